@@ -1,9 +1,26 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X path-tracing hot path (BASELINE.json metric and configs).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]   (N > 1: starts N ranks itself)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
+                                                                     (N > 1: starts N ranks itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W [--workload NAME]
+
+A plain run does what the headline figure needs and nothing else: it sets the device up, warms up,
+times the K steps, writes the outputs if --dump-outputs is given, and prints the result line (metric,
+value, ms_per_step, the workload and the launch-chain counts).  --full adds everything else the
+benchmark measures or checks, each of which takes runs of its own: the untimed per-launch event
+pairs, the exact work counts of the timed launches and the roofline built from them, the launch
+variant, the sampled-row check of a gathered image (--verify-rows), the configs[4] strong-scaling
+leg beside the default line, the output stage, and the CPU baseline.
+
+--dump-outputs DIR writes DIR/image.npy (float32, H x W x 3): the accumulator as the last timed step
+left it -- what a caller of the timed path holds then (N > 1: the image gathered to rank 0).  An
+image above 64 MB is written as a fixed, seeded sample of its rows (DUMP_SEED; the same rows in every
+run).  The steps accumulate progressively, so the dumped run starts its accumulator and its frame
+counter afresh after the device warm-up (whose length is a time budget, not a step count): the image
+then holds frames [1, 1 + (W + K) x spp) whatever the warm-up took, the same from run to run and
+from build to build.
 
 Default workload (configs[1], c2_1080p): 1920x1080, 8 spp, 8 bounces, the demofox quad+sphere
 scene, diffuse+emissive.  One STEP = one launch that accumulates 8 more frames (8 spp) into the
@@ -22,14 +39,15 @@ Scaling modes (the workload's `scaling`, config.py):
           rank 0.  Per-step render and gather times are reported (render_ms_per_step, gather_ms).
 
 PT_BENCH_REHEARSE=1 runs the N-rank code on ONE GPU (every rank on cuda:0, gloo, gathers through
-host memory): correctness of the multi-rank path, not scaling numbers; --verify-rows (default 2
-when rehearsing) then checks sampled rows of rank 0's gathered image against a single-rank render
+host memory): correctness of the multi-rank path, not scaling numbers; with --full, --verify-rows
+(default 2 when rehearsing) then checks sampled rows of rank 0's gathered image against a single-rank render
 of the same rows and frames, bit for bit.
 
-Printed (rank 0, one JSON line): the BASELINE metric (ray-samples/s = pixels x spp x bounces / s),
-ms per step, a roofline object for the render kernel (algorithmic FP32 FLOP/s against the 157.3
-TFLOP/s FP32 vector peak; HBM traffic from the committed rocprofv3 PMC pass), and the CPU baseline
-(the oracle's C restatement of the reference scalar path on this host's cores, bounded sample).
+Printed (rank 0, one JSON line): the BASELINE metric (ray-samples/s = pixels x spp x bounces / s) and
+ms per step; with --full also a roofline object for the render kernel (algorithmic FP32 FLOP/s
+against the 157.3 TFLOP/s FP32 vector peak; HBM traffic from the committed rocprofv3 PMC pass), and
+the CPU baseline (the oracle's C restatement of the reference scalar path on this host's cores,
+bounded sample).
 """
 from __future__ import annotations
 
@@ -61,20 +79,28 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c2_1080p")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: per-launch event pairs, work counts and roofline, launch variant, "
+                         "--verify-rows, the configs[4] leg, the output stage and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the accumulator as the last step left it to DIR/image.npy "
+                         "(float32; above 64 MB a fixed seeded sample of its rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-chain", action="store_true",
                     help="plain pt_render_device / pt_v4_render_device steps, one after the other, instead of chained "
                          "launches (pt_render_device_chain) that overlap consecutive steps")
     ap.add_argument("--no-configs4", action="store_true",
-                    help="default workload: skip the configs[4] strong-scaling leg (c5_8k, a few steps)")
+                    help="--full, default workload: skip the configs[4] strong-scaling leg (c5_8k, a few steps)")
     ap.add_argument("--device-warmup-ms", type=float, default=60.0,
                     help="untimed GPU work before the warmup steps (clock ramp; 0 = none)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
                     help="wall time of the CPU baseline sample (whole frames of the workload)")
     ap.add_argument("--verify-rows", type=int, default=None,
-                    help="rank 0: compare this many sampled rows of the gathered image with a single-rank "
+                    help="--full, rank 0: compare this many sampled rows of the gathered image with a single-rank "
                          "render of the same rows (default 2 with PT_BENCH_REHEARSE=1, else 0)")
     a = ap.parse_args(argv)
+    if a.verify_rows and not a.full:
+        ap.error("--verify-rows needs --full")
     return a
 
 
@@ -232,6 +258,30 @@ def weak_image(W: int, H: int, world: int) -> tuple[int, int]:
     return Wg, Hg
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, image) -> dict:
+    """--dump-outputs: `image` (H x W x 3 f32 tensor, the accumulator after the last timed step) to
+    out_dir/image.npy; above DUMP_MAX_BYTES the rows a generator seeded with DUMP_SEED picks (sorted,
+    as many as fit), the same rows for the same image size."""
+    import numpy as np
+    import torch
+    H, W = int(image.shape[0]), int(image.shape[1])
+    row_bytes = W * 3 * 4
+    sampled = None
+    if H * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(H, size=DUMP_MAX_BYTES // row_bytes, replace=False))
+        image = image[torch.as_tensor(rows, device=image.device)]
+        sampled = {"rows": len(rows), "of": H, "seed": DUMP_SEED}
+    arr = np.ascontiguousarray(image.cpu().numpy(), dtype=np.float32)
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "image.npy", arr)
+    return {"dir": str(out), "arrays": {"image": {"shape": list(arr.shape), "dtype": "float32", "sampled": sampled}}}
+
+
 def job_image(wl, world: int) -> tuple[int, int]:
     """The global image of an N-rank run: fixed for strong scaling (configs[4]), grown for weak."""
     if wl.scaling == "strong":
@@ -374,7 +424,10 @@ def run(args, wl, rank: int, world: int, ops, render_fn, count_fn, *, rehearse: 
     (pt_render_device_chain): the weak-scaling steps are then chained launches -- consecutive steps
     overlap on the GPU, each pixel's frames still folded in order -- and the line reports
     how many of the timed launches continued the overlap.  Strong-scaling steps (a gather of the image
-    between them) are never chained."""
+    between them) are never chained.
+    args.full: after the timed steps also the sampled-row check, the per-launch event pairs and the
+    work counts (each runs launches of its own) and the figures built from them; without it the line
+    holds what the timed steps alone give.  args.dump_outputs: see dump_outputs."""
     import torch
     import torch.distributed as dist
     from cpuperformanceraytracer_amd import roofline as RL
@@ -387,7 +440,8 @@ def run(args, wl, rank: int, world: int, ops, render_fn, count_fn, *, rehearse: 
     mr = max_rows(world, Hg)
     buf = ops.zeros(mr * Wg * 3)
     K = args.steps if args.steps is not None else default_steps(wl)
-    verify_rows = args.verify_rows if args.verify_rows is not None else (2 if rehearse else 0)
+    full_report = args.full
+    verify_rows = (args.verify_rows if args.verify_rows is not None else (2 if rehearse else 0)) if full_report else 0
     frame = 1
 
     chained = chain_counts is not None and not strong
@@ -422,6 +476,13 @@ def run(args, wl, rank: int, world: int, ops, render_fn, count_fn, *, rehearse: 
         ops.sync()
         dw_ms += ops.elapsed_ms(e0, e1)
         dw_steps += batch
+    if args.dump_outputs:
+        # the dumped image must not depend on how many steps the warm-up's time budget took: start
+        # the accumulator and the frames afresh (synchronised: a continuing chained launch does not
+        # wait for work enqueued on the caller's stream)
+        buf.zero_()
+        ops.sync()
+        frame = 1
     for _ in range(args.warmup):
         step(frame)
         frame += S
@@ -485,6 +546,10 @@ def run(args, wl, rank: int, world: int, ops, render_fn, count_fn, *, rehearse: 
         if rank == 0:
             assert full is not None and tuple(full.shape) == (Hg, Wg, 3)
 
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before any later pass accumulates further frames into buf
+        dumped = dump_outputs(args.dump_outputs, full if world > 1 else buf[:Hg * Wg * 3].reshape(Hg, Wg, 3))
+
     verified = None
     if rank == 0 and verify_rows > 0 and full is not None:
         # the gathered rows against a single-rank render of the same rows and frames (frames
@@ -504,79 +569,11 @@ def run(args, wl, rank: int, world: int, ops, render_fn, count_fn, *, rehearse: 
         if bad:
             raise AssertionError(f"gathered rows {bad} differ from the single-rank render")
 
-    # Untimed: per-launch event pairs (the event overhead lands inside each pair).
-    pairs = [(ops.event(), ops.event()) for _ in range(min(K, 20))]
-    for a, b in pairs:
-        ops.record(a)
-        step(frame)
-        ops.record(b)
-        frame += S
-    ops.sync()
-    pair_ms = [ops.elapsed_ms(a, b) for a, b in pairs]
-
-    # Exact work of the timed launches (deterministic: same frames, counted on a scratch buffer).
-    scratch = ops.zeros(mr * Wg * 3)
-    segs = samples = slots = prim = escaped = sky = 0
-    for k in range(K):
-        c = count_fn(scratch, Wg, Hg, timed_first + k * S, S, row_start, row_stride, nrows)
-        escaped += c["escaped"]
-        segs += c["segments"]
-        samples += c["samples"]
-        slots += c["lane_slots"]
-        prim += c.get("primary", c["samples"])
-        sky += c.get("sky_skipped", 0)
-    del scratch
-    if world > 1:   # whole-job work: summed over ranks
-        segs, samples, slots, prim, escaped, sky = (
-            int(v) for v in all_ranks([segs, samples, slots, prim, escaped, sky], dist.ReduceOp.SUM))
-    if rank != 0:
-        return None
-
     v4 = wl.renderer == "v4"
     ms_step = elapsed * 1e3 / K
     total_ray_samples = Wg * Hg * S * B * K
     value = total_ray_samples / elapsed
     avg_kernel_s = launch_ms_avg / 1e3
-    # per-launch figures of ONE rank's kernel (the roofline is per GPU): the whole-job counts / world
-    per_rank = 1.0 / world
-    if v4:   # every frame traces its own jittered camera ray
-        flops_launch = RL.v4_launch_flops(segs, samples) / K * per_rank
-        flops_launch_ref = flops_launch
-        flop_model = (f"segments x V4_F_SEGMENT + samples x V4_F_SAMPLE; F = {RL.V4_F_SEGMENT}/{RL.V4_F_SAMPLE} "
-                      "(roofline.py, counted by oracle/pt_oracle_v4.c)")
-        # pt_v4.hip launch_t: the continuous-tiles kernel for launches of >= 4 8-frame chunks per
-        # resident wave (6144 at its 6 waves per SIMD on MI355X), the per-tile pool kernel else (this
-        # label mirrors that rule)
-        tiles = ((Wg + 7) // 8) * (((Hg + world - 1) // world + 7) // 8)
-        v4_ct = os.environ.get("PT_MI355_NO_CT") != "1" and S >= 8 and (
-            os.environ.get("PT_MI355_V4_CT") == "1" or S * tiles >= 4 * 8 * 6144)
-        kernel_name = "pt_v4_ct_kernel<EQUIRECT, INTERLEAVED>" if v4_ct else "pt_v4_kernel<EQUIRECT, INTERLEAVED>"
-    else:
-        env_esc = escaped if wl.env else 0
-        flops_launch = RL.launch_flops_alg(segs, samples, env_esc) / K * per_rank
-        flops_launch_ref = RL.launch_flops_ref(segs, prim, samples, env_esc) / K * per_rank
-        flop_model = ("algorithmic (SURVEY.md §8d) = device-counted segments x F_SEGMENT + samples x F_SAMPLE"
-                      + (" + escaped paths x F_ENV_ESCAPE" if wl.env else "") +
-                      f"; F = {RL.F_SEGMENT}/{RL.F_SAMPLE}" + (f"/{RL.F_ENV_ESCAPE}" if wl.env else "") +
-                      " (roofline.py; a pixel's camera ray is one segment)")
-        # the continuous-tiles kernels (pt_kernel.hip render_body_ct) unless PT_MI355_NO_CT=1
-        ct = os.environ.get("PT_MI355_NO_CT") != "1"
-        kernel_name = (("pt_render_ct_env_kernel" if ct else "pt_render_env_kernel") if wl.env else
-                       ("pt_render_ct_kernel" if ct else "pt_render_kernel")) + "<INTERLEAVED>"
-    achieved_tf = flops_launch / avg_kernel_s / 1e12
-    pmc = load_pmc(wl.name) if roofline else {}
-    # config 4: one 12-byte texel gather per escaping path
-    env_bytes = RL.BYTES_PER_ENV_GATHER * escaped / K * per_rank if wl.env else 0
-    alg_bytes = RL.BYTES_PER_PIXEL_PER_LAUNCH * Wg * nrows + env_bytes
-    valu = None
-    if pmc.get("sq_insts_valu_per_launch"):
-        valu = {"wave_insts_per_launch": pmc["sq_insts_valu_per_launch"],
-                "per_simd_per_ns": pmc["sq_insts_valu_per_launch"] / (avg_kernel_s * 1e9 * 1024.0),
-                "ceiling_2cycle_ops": 1.0,
-                "source": pmc.get("source"),
-                "note": "SQ_INSTS_VALU of the committed PMC pass over this run's kernel time and the 1024 SIMDs; "
-                        "2-cycle f32 ops issue at ~1.0 per SIMD per ns, the 4-cycle class (compares, selects, "
-                        "min/max, f64, conversions) at ~0.58 (DESIGN.md §3)"}
     launch_chain = {"enabled": False}
     if chained:
         launch_chain = {"enabled": True, "timed_restarts": cc1["restarts"] - cc0["restarts"],
@@ -609,35 +606,10 @@ def run(args, wl, rank: int, world: int, ops, render_fn, count_fn, *, rehearse: 
                             if strong else f"one launch accumulating {S} frames (spp) of every pixel in HBM")},
         "primary_samples_per_s": Wg * Hg * S * K / elapsed,
         "ms_per_frame_1spp": ms_step / S,
-        "traced_segments_per_s": segs / (avg_kernel_s * K),
-        "segments_per_sample": segs / samples,
-        "ref_segments_per_sample": (segs if v4 else RL.ref_segments(segs, prim, samples)) / samples,
-        "simd_lane_efficiency": segs / slots if slots else None,
-        "sky_skipped_traces_per_launch": sky / K * per_rank,
         "launch_chain": launch_chain,
         "kernel_ms_avg": avg_kernel_s * 1e3,
         "kernel_ms_source": ("per step: HIP events around the render launch on its stream (max over ranks)" if strong
                              else "HIP events bracketing the K timed launches on their stream, interval / K"),
-        "kernel_ms_event_pairs": {"launches": len(pair_ms), "avg": sum(pair_ms) / len(pair_ms), "min": min(pair_ms),
-                                  "note": "untimed pass, an event pair around each launch"},
-        "roofline": {
-            "bound": "valu",
-            "achieved": achieved_tf,
-            "peak": RL.PEAK_FP32_TFLOPS,
-            "unit": "TFLOP/s",
-            "frac": achieved_tf / RL.PEAK_FP32_TFLOPS,
-            "traffic": pmc.get("hbm_bytes_per_launch"),
-            "kernel": kernel_name,
-            "flops_per_launch": flops_launch,
-            "flop_model": flop_model,
-            "flops_per_launch_ref_equivalent": flops_launch_ref,
-            "achieved_ref_equivalent": flops_launch_ref / avg_kernel_s / 1e12,
-            "algorithmic_bytes_per_launch": alg_bytes,
-            "hbm_achieved_gbps": alg_bytes / avg_kernel_s / 1e9,
-            "hbm_peak_gbps": RL.PEAK_HBM_GBPS,
-            "traffic_source": pmc.get("source"),
-            "valu_issue": valu,
-        },
     }
     if world > 1:
         res["gather_ms"] = gather_ms / K if strong else gather_ms
@@ -649,6 +621,105 @@ def run(args, wl, rank: int, world: int, ops, render_fn, count_fn, *, rehearse: 
             res["rehearsal"] = "PT_BENCH_REHEARSE=1: all ranks on one GPU, gloo, host-memory gather (not scaling numbers)"
     if verified is not None:
         res["verified"] = verified
+    if dumped is not None:
+        res["outputs"] = dumped
+    res["full"] = full_report
+    if full_report:
+        # Untimed: per-launch event pairs (the event overhead lands inside each pair).
+        pairs = [(ops.event(), ops.event()) for _ in range(min(K, 20))]
+        for a, b in pairs:
+            ops.record(a)
+            step(frame)
+            ops.record(b)
+            frame += S
+        ops.sync()
+        pair_ms = [ops.elapsed_ms(a, b) for a, b in pairs]
+
+        # Exact work of the timed launches (deterministic: same frames, counted on a scratch buffer).
+        scratch = ops.zeros(mr * Wg * 3)
+        segs = samples = slots = prim = escaped = sky = 0
+        for k in range(K):
+            c = count_fn(scratch, Wg, Hg, timed_first + k * S, S, row_start, row_stride, nrows)
+            escaped += c["escaped"]
+            segs += c["segments"]
+            samples += c["samples"]
+            slots += c["lane_slots"]
+            prim += c.get("primary", c["samples"])
+            sky += c.get("sky_skipped", 0)
+        del scratch
+        if world > 1:   # whole-job work: summed over ranks
+            segs, samples, slots, prim, escaped, sky = (
+                int(v) for v in all_ranks([segs, samples, slots, prim, escaped, sky], dist.ReduceOp.SUM))
+    if rank != 0:
+        return None
+    if full_report:
+        # per-launch figures of ONE rank's kernel (the roofline is per GPU): the whole-job counts / world
+        per_rank = 1.0 / world
+        if v4:   # every frame traces its own jittered camera ray
+            flops_launch = RL.v4_launch_flops(segs, samples) / K * per_rank
+            flops_launch_ref = flops_launch
+            flop_model = (f"segments x V4_F_SEGMENT + samples x V4_F_SAMPLE; F = {RL.V4_F_SEGMENT}/{RL.V4_F_SAMPLE} "
+                          "(roofline.py, counted by oracle/pt_oracle_v4.c)")
+            # pt_v4.hip launch_t: the continuous-tiles kernel for launches of >= 4 8-frame chunks per
+            # resident wave (6144 at its 6 waves per SIMD on MI355X), the per-tile pool kernel else (this
+            # label mirrors that rule)
+            tiles = ((Wg + 7) // 8) * (((Hg + world - 1) // world + 7) // 8)
+            v4_ct = os.environ.get("PT_MI355_NO_CT") != "1" and S >= 8 and (
+                os.environ.get("PT_MI355_V4_CT") == "1" or S * tiles >= 4 * 8 * 6144)
+            kernel_name = "pt_v4_ct_kernel<EQUIRECT, INTERLEAVED>" if v4_ct else "pt_v4_kernel<EQUIRECT, INTERLEAVED>"
+        else:
+            env_esc = escaped if wl.env else 0
+            flops_launch = RL.launch_flops_alg(segs, samples, env_esc) / K * per_rank
+            flops_launch_ref = RL.launch_flops_ref(segs, prim, samples, env_esc) / K * per_rank
+            flop_model = ("algorithmic (SURVEY.md §8d) = device-counted segments x F_SEGMENT + samples x F_SAMPLE"
+                          + (" + escaped paths x F_ENV_ESCAPE" if wl.env else "") +
+                          f"; F = {RL.F_SEGMENT}/{RL.F_SAMPLE}" + (f"/{RL.F_ENV_ESCAPE}" if wl.env else "") +
+                          " (roofline.py; a pixel's camera ray is one segment)")
+            # the continuous-tiles kernels (pt_kernel.hip render_body_ct) unless PT_MI355_NO_CT=1
+            ct = os.environ.get("PT_MI355_NO_CT") != "1"
+            kernel_name = (("pt_render_ct_env_kernel" if ct else "pt_render_env_kernel") if wl.env else
+                           ("pt_render_ct_kernel" if ct else "pt_render_kernel")) + "<INTERLEAVED>"
+        achieved_tf = flops_launch / avg_kernel_s / 1e12
+        pmc = load_pmc(wl.name) if roofline else {}
+        # config 4: one 12-byte texel gather per escaping path
+        env_bytes = RL.BYTES_PER_ENV_GATHER * escaped / K * per_rank if wl.env else 0
+        alg_bytes = RL.BYTES_PER_PIXEL_PER_LAUNCH * Wg * nrows + env_bytes
+        valu = None
+        if pmc.get("sq_insts_valu_per_launch"):
+            valu = {"wave_insts_per_launch": pmc["sq_insts_valu_per_launch"],
+                    "per_simd_per_ns": pmc["sq_insts_valu_per_launch"] / (avg_kernel_s * 1e9 * 1024.0),
+                    "ceiling_2cycle_ops": 1.0,
+                    "source": pmc.get("source"),
+                    "note": "SQ_INSTS_VALU of the committed PMC pass over this run's kernel time and the 1024 SIMDs; "
+                            "2-cycle f32 ops issue at ~1.0 per SIMD per ns, the 4-cycle class (compares, selects, "
+                            "min/max, f64, conversions) at ~0.58 (DESIGN.md §3)"}
+        res.update({
+            "traced_segments_per_s": segs / (avg_kernel_s * K),
+            "segments_per_sample": segs / samples,
+            "ref_segments_per_sample": (segs if v4 else RL.ref_segments(segs, prim, samples)) / samples,
+            "simd_lane_efficiency": segs / slots if slots else None,
+            "sky_skipped_traces_per_launch": sky / K * per_rank,
+            "kernel_ms_event_pairs": {"launches": len(pair_ms), "avg": sum(pair_ms) / len(pair_ms), "min": min(pair_ms),
+                                      "note": "untimed pass, an event pair around each launch"},
+            "roofline": {
+                "bound": "valu",
+                "achieved": achieved_tf,
+                "peak": RL.PEAK_FP32_TFLOPS,
+                "unit": "TFLOP/s",
+                "frac": achieved_tf / RL.PEAK_FP32_TFLOPS,
+                "traffic": pmc.get("hbm_bytes_per_launch"),
+                "kernel": kernel_name,
+                "flops_per_launch": flops_launch,
+                "flop_model": flop_model,
+                "flops_per_launch_ref_equivalent": flops_launch_ref,
+                "achieved_ref_equivalent": flops_launch_ref / avg_kernel_s / 1e12,
+                "algorithmic_bytes_per_launch": alg_bytes,
+                "hbm_achieved_gbps": alg_bytes / avg_kernel_s / 1e9,
+                "hbm_peak_gbps": RL.PEAK_HBM_GBPS,
+                "traffic_source": pmc.get("source"),
+                "valu_issue": valu,
+            },
+        })
     res["_accumulator"] = buf   # (popped by main: the output stage runs on the rendered accumulator)
     return res
 
@@ -660,7 +731,7 @@ def strong_leg(wl4, rank: int, world: int, ops, render_fn, count_fn, *, rehearse
     gather of the sub-images to rank 0 (both timed, reported separately), a few steps -- so the
     driver's N = 1, 2, 4, 8 runs of the default line also trace configs[4]'s scaling curve.  The
     gathered image is checked against a single-rank render of two rows.  Rank 0 returns a summary."""
-    a4 = parse(["--gpus", str(world), "--steps", str(steps), "--warmup", "1", "--device-warmup-ms", "0",
+    a4 = parse(["--gpus", str(world), "--steps", str(steps), "--warmup", "1", "--device-warmup-ms", "0", "--full",
                 "--verify-rows", "2" if world > 1 else "0"])
     r = run(a4, wl4, rank, world, ops, render_fn, count_fn, rehearse=rehearse, roofline=False)
     if r is None:
@@ -696,9 +767,9 @@ class Hooks:
 
 def drive(args, wl, rank: int, world: int, ops, render_fn, count_fn, hooks: Hooks, *,
           rehearse: bool = False, leg_workload=None) -> dict | None:
-    """Everything main() does after the device is set up, on every rank: the timed job (run), the
-    reports that need only the rank's own state, the configs[4] strong leg of the default line (all
-    ranks take part: it gathers), then rank 0's output stage and CPU baseline.  Returns rank 0's JSON
+    """Everything main() does after the device is set up, on every rank: the timed job (run) and, with
+    args.full, the reports that need only the rank's own state, the configs[4] strong leg of the default
+    line (all ranks take part: it gathers), then rank 0's output stage and CPU baseline.  Returns rank 0's JSON
     object, None on the other ranks -- whose only duty after run() is to take part in the leg's
     collectives (a report that assumed a result dict there crashed ranks 1..N-1 before the leg and
     left rank 0 waiting in its all-reduce: ADVICE round 5).  leg_workload: the strong leg's workload
@@ -723,7 +794,7 @@ def drive(args, wl, rank: int, world: int, ops, render_fn, count_fn, hooks: Hook
     acc = None
     if res is not None:
         acc = res.pop("_accumulator")
-        if hooks.launch_variant is not None:   # the continuous-tiles launch variant (pt_launch_variant)
+        if args.full and hooks.launch_variant is not None:   # the continuous-tiles launch variant (pt_launch_variant)
             Wg, Hg = job_image(wl, world)
             rs, st, nr = rows_of(rank, world, Hg)
             try:   # (a report: it never costs the line)
@@ -732,12 +803,14 @@ def drive(args, wl, rank: int, world: int, ops, render_fn, count_fn, hooks: Hook
                 res["launch_variant"] = {"error": str(e)}
     # configs[4] beside the default workload's line (its scaling curve from the driver's N-GPU runs)
     configs4 = None
-    if args.workload == "c2_1080p" and not args.no_configs4:
+    if args.full and args.workload == "c2_1080p" and not args.no_configs4:
         from cpuperformanceraytracer_amd.config import CONFIGS
         configs4 = strong_leg(leg_workload or CONFIGS["c5_8k"], rank, world, ops, render_fn, count_fn, rehearse=rehearse)
         hooks.check_errors()
     if rank != 0:
         return None
+    if not args.full:
+        return res
     if hooks.output_stage is not None:
         res["output_stage"] = hooks.output_stage(acc, res)
     if configs4 is not None:

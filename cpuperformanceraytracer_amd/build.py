@@ -142,7 +142,11 @@ def build_oracle(verbose: bool = False) -> None:
     using it: the product never loads either."""
     subprocess.run(["make", "-s", "-C", str(ROOT / "oracle")], check=True)
     ref = Path("/root/reference/CPUPerformanceRayTracer")
-    if ref.exists():
+    try:
+        have_ref = ref.exists()
+    except OSError:   # (a parent directory this user may not enter: as good as absent)
+        have_ref = False
+    if have_ref:
         subprocess.run([str(ROOT / "oracle" / "build_ref.sh")], check=True,
                        stdout=None if verbose else subprocess.DEVNULL)
 

@@ -6,7 +6,7 @@ set -uo pipefail
 TAG=$1; R=${2:-2}; WL=${3:-c2_1080p}
 OUT=gpurun_out/$TAG; mkdir -p "$OUT"
 export TMPDIR=/tmp
-B=(python3 bench.py --workload "$WL" --steps 200 --no-cpu-baseline --no-configs4)
+B=(python3 bench.py --workload "$WL" --steps 200 --full --no-cpu-baseline --no-configs4)
 for r in $(seq "$R"); do
     PT_MI355_LIB=$PWD/build/libpt_prechain.so timeout -k 10 200 "${B[@]}" --no-chain > "$OUT/pre_$r.json" 2> "$OUT/pre_$r.err" || exit 1
     timeout -k 10 200 "${B[@]}" --no-chain > "$OUT/plain_$r.json" 2> "$OUT/plain_$r.err" || exit 1

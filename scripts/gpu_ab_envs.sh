@@ -13,7 +13,7 @@ for r in $(seq "$R"); do
         extra=()
         [ "$v" = "-" ] && v=""
         case " $v " in *" NOCHAIN=1 "*) extra=(--no-chain) ;; esac
-        env $v timeout -k 10 200 python3 bench.py --workload "$WL" --steps 200 --no-cpu-baseline --no-configs4 "${extra[@]}" \
+        env $v timeout -k 10 200 python3 bench.py --workload "$WL" --steps 200 --full --no-cpu-baseline --no-configs4 "${extra[@]}" \
             > "$OUT/v${i}_$r.json" 2> "$OUT/v${i}_$r.err" || { tail -5 "$OUT/v${i}_$r.err"; exit 1; }
         python3 -c "import json;d=json.loads(open('$OUT/v${i}_$r.json').read().strip().splitlines()[-1]);print('[$v]', $r, round(d['ms_per_step'], 5), round(d['roofline']['frac'], 4), d.get('launch_variant'), {k: v for k, v in d.get('launch_chain', {}).items() if k != 'note'})" | tee -a "$OUT/summary.txt"
     done

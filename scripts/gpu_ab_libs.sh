@@ -6,7 +6,7 @@ set -uo pipefail
 TAG=$1; R=$2; WL=$3; shift 3
 OUT=gpurun_out/$TAG; mkdir -p "$OUT"
 export TMPDIR=/tmp
-B=(python3 bench.py --workload "$WL" --steps 200 --no-cpu-baseline --no-configs4)
+B=(python3 bench.py --workload "$WL" --steps 200 --full --no-cpu-baseline --no-configs4)
 for r in $(seq "$R"); do
     for v in "$@"; do
         n=$(basename "$v" .so)

@@ -7,9 +7,9 @@ TAG=${1:-bench}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 300 python bench.py > "$OUT/bench_c2_1080p.json" 2> "$OUT/bench_c2_1080p.err"
+timeout -k 10 300 python bench.py --full > "$OUT/bench_c2_1080p.json" 2> "$OUT/bench_c2_1080p.err"
 for wl in c3_4k c4_env_1080p v4_1080p c5_8k; do
-    timeout -k 10 300 python bench.py --workload $wl --no-cpu-baseline > "$OUT/bench_$wl.json" 2> "$OUT/bench_$wl.err"
+    timeout -k 10 300 python bench.py --workload $wl --full --no-cpu-baseline > "$OUT/bench_$wl.json" 2> "$OUT/bench_$wl.err"
 done
 python - "$OUT" <<'PY'
 import json, sys, glob

@@ -14,8 +14,8 @@ timeout -k 10 800 python -u -m pytest tests/test_gpu_chain.py -x -v --timeout 40
 tail -15 "$OUT/chain_tests.log"
 WL=${WORKLOADS:-c2_1080p}
 for wl in $WL; do
-    timeout -k 10 200 python bench.py --workload "$wl" --no-cpu-baseline --no-configs4 > "$OUT/bench_chain_$wl.json" 2> "$OUT/bench_chain_$wl.err" || { tail -20 "$OUT/bench_chain_$wl.err"; exit 1; }
-    timeout -k 10 200 python bench.py --workload "$wl" --no-cpu-baseline --no-configs4 --no-chain > "$OUT/bench_nochain_$wl.json" 2> "$OUT/bench_nochain_$wl.err" || { tail -20 "$OUT/bench_nochain_$wl.err"; exit 1; }
+    timeout -k 10 200 python bench.py --workload "$wl" --full --no-cpu-baseline --no-configs4 > "$OUT/bench_chain_$wl.json" 2> "$OUT/bench_chain_$wl.err" || { tail -20 "$OUT/bench_chain_$wl.err"; exit 1; }
+    timeout -k 10 200 python bench.py --workload "$wl" --full --no-cpu-baseline --no-configs4 --no-chain > "$OUT/bench_nochain_$wl.json" 2> "$OUT/bench_nochain_$wl.err" || { tail -20 "$OUT/bench_nochain_$wl.err"; exit 1; }
 done
 for f in $(for wl in $WL; do echo bench_chain_$wl bench_nochain_$wl; done); do
     python3 -c "import json;d=json.loads(open('$OUT/$f.json').read().strip().splitlines()[-1]);print('$f', d['ms_per_step'], '%.3e' % d['value'], round(d['roofline']['frac'], 4), d.get('launch_chain'))"

@@ -8,7 +8,7 @@ set -euo pipefail
 TAG=${1:-coverage}; OUT=$PWD/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-PT_BENCH_REHEARSE=1 timeout -k 10 600 python3 bench.py --gpus 2 --steps 5 > "$OUT/rehearse_c2_n2.json" 2> "$OUT/rehearse.err" || { tail -30 "$OUT/rehearse.err"; exit 1; }
+PT_BENCH_REHEARSE=1 timeout -k 10 600 python3 bench.py --gpus 2 --steps 5 --full > "$OUT/rehearse_c2_n2.json" 2> "$OUT/rehearse.err" || { tail -30 "$OUT/rehearse.err"; exit 1; }
 python3 -c "import json;d=json.loads(open('$OUT/rehearse_c2_n2.json').read().strip().splitlines()[-1]);print('rehearsal', d['n_gpus'], d['ms_per_step'], d['config']['image'], d['configs4']['verified'], d.get('launch_variant'))"
 timeout -k 10 1000 rocprofv3 --kernel-trace --output-format csv -d "$OUT/prof" -o suite -- python3 -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread -p no:cacheprovider > "$OUT/suite.log" 2>&1 || { tail -30 "$OUT/suite.log"; exit 1; }
 tail -2 "$OUT/suite.log"

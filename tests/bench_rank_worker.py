@@ -31,7 +31,7 @@ def main() -> int:
     try:
         wl = Workload("tiny", w, h, spp, b, scaling=scaling)
         args = bench.parse(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--device-warmup-ms", "0",
-                            "--verify-rows", "2"])
+                            "--full", "--verify-rows", "2"])
 
         def render_fn(buf, W, H, f, n, rs, st, nr):
             pyoracle.render(W, H, frame_first=f, nframes=n, num_bounces=b, row_start=rs, row_stride=st, nrows=nr,

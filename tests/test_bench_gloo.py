@@ -53,7 +53,7 @@ def _worker(rank, world, port, scaling, q, skew=False):
     try:
         wl = Workload("tiny", 64, 36, 3, 8, scaling=scaling)   # configs[4]'s shape, scaled down
         args = bench.parse(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--device-warmup-ms",
-                            "20" if skew else "0", "--verify-rows", "2"])
+                            "20" if skew else "0", "--full", "--verify-rows", "2"])
 
         def render_fn(buf, W, H, f, n, rs, st, nr):
             pyoracle.render(W, H, frame_first=f, nframes=n, num_bounces=wl.num_bounces, row_start=rs,
@@ -288,7 +288,8 @@ def _worker_drive(rank, world, port, q):
     try:
         wl = Workload("tiny", 64, 36, 3, 8, scaling="weak")
         wl4 = Workload("tiny_c5", 48, 28, 4, 8, scaling="strong")
-        args = bench.parse(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--device-warmup-ms", "0"])
+        args = bench.parse(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--device-warmup-ms", "0",
+                            "--full"])
 
         def render_fn(buf, W, H, f, n, rs, st, nr):
             pyoracle.render(W, H, frame_first=f, nframes=n, num_bounces=8, row_start=rs, row_stride=st, nrows=nr,

@@ -2,12 +2,14 @@
 
 Pinned against the reference's vendored stb_image v2.26, compiled from the reference's sources
 by oracle/build_ref.sh (oracle/_ref/ref_hdr): bit-identical texels on every texture the reference
-ships (when /root/reference is present) and on synthetic files covering each scanline encoding
-stb accepts.  The decoder is host code inside libpt_mi355.so, so these run without a GPU.
+ships (stored under tests/golden/textures with the shape and sha256 of stb's texels; compared with
+stb's texels themselves where oracle/_ref/ref_hdr is built) and on synthetic files covering each
+scanline encoding stb accepts.  The decoder is host code inside libpt_mi355.so, so these run without a GPU.
 """
 from __future__ import annotations
 
 import hashlib
+import json
 import subprocess
 from pathlib import Path
 
@@ -19,7 +21,8 @@ from cpuperformanceraytracer_amd import _native as N
 from cpuperformanceraytracer_amd.renderer import DecodeHdr
 
 ROOT = Path(__file__).resolve().parents[1]
-REF_TEXTURES = Path("/root/reference/Textures")
+REF_TEXTURES = ROOT / "tests" / "golden" / "textures"
+STB_TEXELS = json.loads((REF_TEXTURES / "stb_texels.json").read_text())["textures"]
 REF_HDR = ROOT / "oracle" / "_ref" / "ref_hdr"
 # sha256 of the f32 texels stb_image decodes from HDR_040_Field_Env.hdr (512 x 256 x 3, flipped)
 FIELD_ENV_SHA256 = "e1b72594c8b294b1905bc941249b40a9f9da0ab5a7a1df79cc8bc63eda50ea5c"
@@ -151,7 +154,6 @@ def test_missing_file_raises(tmp_path):
         pt.LoadTexture(tmp_path / "nope.hdr")
 
 
-@pytest.mark.skipif(not (REF_TEXTURES / "HDR_040_Field_Env.hdr").exists(), reason="reference textures absent")
 def test_field_env_kat():
     """The config-4 parity texture of the reference decodes to stb's texels (sha256 recorded)."""
     _lib_or_skip()
@@ -160,14 +162,17 @@ def test_field_env_kat():
     assert hashlib.sha256(t.Data.tobytes()).hexdigest() == FIELD_ENV_SHA256
 
 
-@pytest.mark.skipif(not REF_HDR.exists() or not REF_TEXTURES.exists(), reason="stb reference build absent")
 @pytest.mark.parametrize("name", ["HDR_040_Field_Env", "px", "nx", "py", "ny", "pz", "nz"])
 def test_reference_textures_match_stb(tmp_path, name):
     _lib_or_skip()
     t = pt.LoadTexture(REF_TEXTURES / f"{name}.hdr")
-    ref = _stb(REF_TEXTURES / f"{name}.hdr", tmp_path)
-    assert t.Data.shape == ref.shape
-    assert np.array_equal(t.Data.view(np.uint32), ref.view(np.uint32))
+    want = STB_TEXELS[name]
+    assert t.Data.dtype == np.float32 and t.Data.shape == (want["height"], want["width"], want["components"])
+    assert hashlib.sha256(t.Data.tobytes()).hexdigest() == want["texels_sha256"]
+    if REF_HDR.exists():   # stb itself, where the reference build is present
+        ref = _stb(REF_TEXTURES / f"{name}.hdr", tmp_path)
+        assert t.Data.shape == ref.shape
+        assert np.array_equal(t.Data.view(np.uint32), ref.view(np.uint32))
 
 
 def test_texture_struct_layout():
