@@ -72,7 +72,18 @@ struct Sched {
     // that stored its pixels (2 ntiles words), and that number of the geometry's last chained launch
     uint32_t* epoch = nullptr;
     uint32_t chain_seq = 0;
+    // camera-hit cache (pt_kernel.h PtJob::cam_cache): one record per pixel of the
+    // geometry's tiles, allocated and filled by its first uncounted continuous-tiles launch of at least
+    // kCamMinFrames frames.  The records depend on the key's pixels (width .. nrows) and on the scene,
+    // which is uploaded once, when the device is set up and has no schedules yet -- so a cache lives
+    // at most as long as its Sched.  nullptr: none (yet); cam_off: the allocation failed, never again.
+    unsigned long long* cam = nullptr;
+    bool cam_off = false;
+    // kCamEmpty; kCamFilled: the geometry's last launch filled it (the next launch is stream-ordered
+    // after it: a chained one restarts); kCamSettled: every later launch may read it
+    uint8_t cam_state = 0;
 };
+enum : uint8_t { kCamEmpty = 0, kCamFilled = 1, kCamSettled = 2 };
 constexpr uint32_t kTuneRounds = 3;   // rounds of the palindromic arm order timed; the first is discarded
 constexpr int kSchedSlots = 16;
 constexpr int kBands = 4;   // PT_FLAG_PIN_HOST: row bands of a pipelined frame
@@ -113,6 +124,7 @@ struct Dev {
     float* denv = nullptr;              // env map in HBM (pt_set_env_map / textured / v4)
     Sched sched[kSchedSlots];
     unsigned long long sched_clock = 0;
+    unsigned long long cam_checked = 0;   // pt_cam_cache_query: records the last pt_count_device launch compared
     float* dtone_in = nullptr;          // output stage scratch
     size_t dtone_in_cap = 0;
     uint32_t* dtone_out = nullptr;
@@ -197,6 +209,7 @@ struct State {
     uint32_t ct_seq_len = 0, ct_seq_pos = 0;
     uint32_t split = 1;   // PT_MI355_SPLIT (read by pt_init): tile split factor of the schedule (0: none)
     int64_t test_bad_entry = -1;   // PT_MI355_TEST_BAD_ENTRY (test hook, pt_init)
+    bool cam_cache = true;   // PT_MI355_CAM_CACHE=0 (read by pt_init): no camera-hit caches (A/B, tests)
     bool no_ct = false;   // PT_MI355_NO_CT=1 (read by pt_init): one-chunk launches on render_body (A/B)
     uint32_t test_chain_delay = 0;   // PT_MI355_TEST_CHAIN_DELAY=<us> (pt_init): chained launches publish late
     uint32_t unit_mult = 2;          // PT_MI355_UNIT_MULT (pt_init, A/B): the diffuse CT schedule's unit multiple
@@ -352,6 +365,8 @@ const char* guard_name(uint32_t id)
         case PT_G_SCHED_UNIT: return "schedule builder: unit index out of range";
         case PT_G_RECORD: return "item record slot >= 64";
         case PT_G_QUEUE_GROUP: return "queue group out of range";
+        case PT_G_CAM_INDEX: return "camera-hit cache record outside the geometry's tiles";
+        case PT_G_CAM_RECORD: return "a traced camera hit differs from its cached record; value: tile * 64 + lane";
         case PT_G_CHAIN_WAIT: return "chained launch: the previous launch's tile never became ready; value: the tile | its epoch's lag "
                                      "<< 24 | bit 31 when an atomic read also lags (pt_chain.h)";
         default: return "unknown";
@@ -383,6 +398,7 @@ int sync_all()
         HIP_TRY(hipMemcpyAsync(dv.derr, dv.herr, sizeof(init), hipMemcpyHostToDevice, dv.stream));
         HIP_TRY(hipStreamSynchronize(dv.stream));
         if (guards && (uint32_t)(first >> 32) == PT_G_CHAIN_WAIT) dv.chain.off = true;
+        for (Sched& sc : dv.sched) sc.cam_state = kCamEmpty;   // (a faulted fill launch leaves records unwritten: fill again)
         if (guards)
             return fail(PT_EKERNEL, "device %d: %u kernel bounds guard failure(s), the first: guard %u (%s), value %u; "
                         "pool guards: %u (first tile %u); the accumulator is invalid", dv.ordinal, guards,
@@ -534,6 +550,8 @@ PtJob base_job(float* buf, int32_t w, int32_t h)
     j.chain_seq = 0;
     j.chain_wait = 0;
     j.started = nullptr;
+    j.cam_cache = nullptr;
+    j.cam_mode = PT_CAM_NONE;
     return j;
 }
 
@@ -543,6 +561,7 @@ void free_sched(Sched& s)
     if (s.order) (void)hipFree(s.order);
     if (s.units) (void)hipFree(s.units);
     if (s.epoch) (void)hipFree(s.epoch);
+    if (s.cam) (void)hipFree(s.cam);
     for (hipEvent_t e : s.tune_ev)
         if (e) (void)hipEventDestroy(e);
     s = Sched{};
@@ -580,6 +599,52 @@ SchedKey sched_key(const PtV4Job& j)
     k.env = j.env;
     k.ntiles = (uint32_t)((j.ncols + 7) / 8) * (uint32_t)((j.nrows + 7) / 8);
     return k;
+}
+
+bool cam_cache_wanted(const SchedKey& key) { return pt_cam_cache_wanted(g.cam_cache, key.kind, key.ntiles); }
+
+// Launches of fewer frames neither fill nor use a cache, and move no cache state.  A tile of such a
+// launch carries few items, and the record load at the tile's start -- a dependent HBM / MALL access
+// right after the claim's atomic -- then costs more than the coherent camera trace it replaces.
+// Measured at 1920 x 1080, parent vs cache for every length (profiles/camcache): 1 frame per launch
+// 0.1142 -> 0.1168 ms (+2.3 %), 8 frames 0.2198 -> 0.2169 (-1.3 %), 16 (env) and 64 (4K) -0.5 %.  The
+// bound is the shortest length measured to gain, one whole chunk (kChunk, pt_kernel.hip).
+constexpr int32_t kCamMinFrames = 8;
+bool cam_launch_qualifies(const Sched& s, int32_t nframes)
+{
+    return !s.cam_off && nframes >= kCamMinFrames && cam_cache_wanted(s.key);
+}
+// A chained launch may continue the overlap (launch_chain) unless it would fill the cache or read
+// records that a launch it may overlap is still writing.
+bool cam_chain_may_continue(const Sched& s, int32_t nframes)
+{
+    return !cam_launch_qualifies(s, nframes) || (s.cam && s.cam_state == kCamSettled);
+}
+
+// The camera-hit cache fields of a launch of `s`'s geometry on `st` that is stream-ordered after the
+// geometry's earlier launches (every launch but a continuing chained one).  A counted launch never
+// fills: it traces the camera rays for its counters, and compares them with a valid cache.
+void cam_cache_job(Sched* s, PtJob& j, bool count, hipStream_t st)
+{
+    j.cam_cache = nullptr;
+    j.cam_mode = PT_CAM_NONE;
+    if (!s || !j.ct_slots || !cam_launch_qualifies(*s, j.nframes)) return;
+    if (s->cam_state == kCamFilled) s->cam_state = kCamSettled;
+    if (s->cam_state == kCamEmpty && count) return;
+    if (!s->cam) {
+        // every record a miss until the fill launch stores it (a tile that a faulted fill launch
+        // abandoned then reads as sky, never as an arbitrary primitive)
+        const size_t bytes = pt_cam_cache_bytes(s->key.ntiles);
+        if (hipMalloc(&s->cam, bytes) != hipSuccess || hipMemsetAsync(s->cam, 0xff, bytes, st) != hipSuccess) {
+            (void)hipGetLastError();
+            if (s->cam) (void)hipFree(s->cam);
+            s->cam = nullptr;
+            s->cam_off = true;   // launches without a cache: correct, only slower
+            return;
+        }
+    }
+    j.cam_cache = s->cam;
+    j.cam_mode = s->cam_state == kCamEmpty ? PT_CAM_FILL : PT_CAM_USE;
 }
 
 Sched* find_sched(Dev& dv, const SchedKey& key, hipStream_t st)
@@ -636,7 +701,8 @@ struct LaunchSched {
     const uint32_t* units = nullptr;
     const uint32_t* nunits = nullptr;
     uint32_t* cost = nullptr;
-    Sched* sched = nullptr;
+    Sched* sched = nullptr;   // with a built schedule
+    Sched* geo = nullptr;     // the geometry's Sched, built or not
 };
 // Order `st` after every chained launch of the device and end the live chain (launch_chain): a
 // launch that is not a continuing chained one may use what the chained launches use -- the slot
@@ -666,6 +732,7 @@ int use_sched(Dev& dv, const SchedKey& key, hipStream_t st, LaunchSched* ls, uin
     int rc;
     if ((rc = chain_join(dv, st))) return rc;
     if (Sched* s = find_sched(dv, key, sched_st ? *sched_st : st)) {
+        ls->geo = s;
         // (re)build the schedule from the last launch's costs on the 2nd launch of a geometry and
         // then every g.sched_rebuild launches (the costs of a fixed view barely change; the builder
         // is a one-workgroup kernel of ~57 us at 1080p)
@@ -871,9 +938,13 @@ int launch(Dev& dv, PtJob j, hipStream_t st, bool count, uint32_t* ct_blocks = n
     j.ct_back_pct = j.nframes <= 16 ? g.ct_back_pct : 0u;
     hipEvent_t* tev = nullptr;
     if ((rc = ct_occupancy(ls, j, &tev, count))) return rc;
+    cam_cache_job(ls.geo, j, count, st);
+    uint32_t blocks = 0;
     if (tev) HIP_TRY(hipEventRecord(tev[0], st));
-    hipError_t e = pt_launch_render(j, st, count, ct_blocks);
+    hipError_t e = pt_launch_render(j, st, count, &blocks);
     if (e != hipSuccess) return fail(PT_EHIP, "render launch failed: %s", hipGetErrorString(e));
+    if (ct_blocks) *ct_blocks = blocks;
+    if (j.cam_mode == PT_CAM_FILL && blocks) ls.geo->cam_state = kCamFilled;   // (a continuous-tiles kernel ran)
     if (tev) HIP_TRY(hipEventRecord(tev[1], st));
     return queue_done(dv, ls.slot, st, j.ncols > 0 && j.nrows > 0 && j.nframes > 0);   // (pt_launch_render's early return)
 }
@@ -971,6 +1042,9 @@ int chain_continue(Dev& dv, PtJob& j, Sched* sc, hipStream_t X, uint32_t* blocks
     hipEvent_t* tev = nullptr;   // (none: the variant is settled)
     if ((rc = ct_occupancy(ls, j, &tev, false))) return rc;
     if (j.ct_back_pct != 0 && !j.env && !g.back_set) j.ct_back_pct = kChainBack;
+    const bool cam_use = sc->cam && cam_launch_qualifies(*sc, j.nframes);   // (settled: launch_chain continues only then)
+    j.cam_cache = cam_use ? sc->cam : nullptr;
+    j.cam_mode = cam_use ? PT_CAM_USE : PT_CAM_NONE;
     hipError_t e = pt_launch_render(j, X, false, blocks);
     if (e != hipSuccess) return fail(PT_EHIP, "render launch failed: %s", hipGetErrorString(e));
     return PT_OK;
@@ -1004,7 +1078,10 @@ int launch_chain(Dev& dv, Job j, hipStream_t s)
     // before it do not write them, and the next launch, which builds from them, restarts)
     const bool builds = sc->have_cost && (!sc->built || sc->launches % g.sched_rebuild == 0);
     const bool records = !sc->built || (sc->launches + 1) % g.sched_rebuild == 0;
-    const bool cont = c.sched == sc && sc->built && !builds && chain_variant_fixed(j, *sc);
+    // (the camera-hit cache: the launch that fills it and the one after it restart -- no launch reads
+    // records while another may still be writing them)
+    const bool cont = c.sched == sc && sc->built && !builds && chain_variant_fixed(j, *sc) &&
+                      cam_chain_may_continue(*sc, j.nframes);
     const uint32_t seq = sc->chain_seq + 1;
     const int par = cont ? c.par ^ 1 : 0;
     hipStream_t X = c.st[par];
@@ -1714,6 +1791,7 @@ int pt_init(const pt_config* cfg)
     HIP_TRY(hipEventCreateWithFlags(&g.ev_q, hipEventDisableTiming));
     g.frame = 0;
     g.ring_guard_cap = ~0u;
+    g.cam_cache = !(getenv("PT_MI355_CAM_CACHE") && !strcmp(getenv("PT_MI355_CAM_CACHE"), "0"));
     g.no_ct = getenv("PT_MI355_NO_CT") && !strcmp(getenv("PT_MI355_NO_CT"), "1");
     g.test_chain_delay = getenv("PT_MI355_TEST_CHAIN_DELAY") ? (uint32_t)strtoul(getenv("PT_MI355_TEST_CHAIN_DELAY"), nullptr, 10) : 0u;
     g.sched_rebuild = getenv("PT_MI355_SCHED_REBUILD") ? std::max<unsigned long long>(2ull, strtoull(getenv("PT_MI355_SCHED_REBUILD"), nullptr, 10))
@@ -2167,6 +2245,29 @@ int pt_count_device(const pt_device_job* dj, void* stream, pt_work_counts* out)
     out->quad_fallbacks = h[PT_CNT_FALLBACK];
     out->sphere_fallbacks = 0;
     out->sky_skipped = h[PT_CNT_SKY];
+    dv->cam_checked = h[PT_CNT_CAM_CHECKED];
+    return PT_OK;
+}
+
+int pt_cam_cache_query(const pt_device_job* dj, void* stream, int32_t* state, uint64_t* compared)
+{
+    int rc;
+    PtJob j;
+    Dev* dv = nullptr;
+    if (!state || !compared) return fail(PT_EINVAL, "null output");
+    *state = PT_CAM_CACHE_NONE;
+    *compared = 0;
+    if ((rc = ensure_init()) || (rc = device_job(dj, &j)) || (rc = dev_of(dj->buf, &dv))) return rc;
+    if (dj->use_env) j.env = dv->denv;
+    *compared = dv->cam_checked;
+    SchedKey key = sched_key(j);
+    key.split = j.nframes <= 8 ? g.split : 0u;   // (as launch())
+    for (const Sched& s : dv->sched) {
+        if (!s.used || s.stream != (hipStream_t)stream || !(s.key == key)) continue;
+        if (s.cam && cam_launch_qualifies(s, j.nframes))
+            *state = s.cam_state == kCamEmpty ? PT_CAM_CACHE_EMPTY : s.cam_state == kCamFilled ? PT_CAM_CACHE_FILLED : PT_CAM_CACHE_SETTLED;
+        break;
+    }
     return PT_OK;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "pt_camcache.h"
 #include "pt_scene.h"
 
 // Output layouts of the reference's frame functions (include/pt_mi355.h documents each).
@@ -20,7 +21,8 @@ enum PtCounter : int {
     PT_CNT_PRIMARY = 4,      // camera-ray segments traced (one per pixel)
     PT_CNT_FALLBACK = 5,     // segments whose culled quad stage ran the six exact tests
     PT_CNT_SKY = 6,          // camera rays whose TestSceneTrace a sky tile skipped (counted in SEGMENTS)
-    PT_CNT_N = 7,
+    PT_CNT_CAM_CHECKED = 7,  // traced camera hits compared with their cached records (PT_CAM_USE; pt_cam_cache_query)
+    PT_CNT_N = 8,
 };
 
 struct PtJob {
@@ -73,6 +75,13 @@ struct PtJob {
     uint32_t chain_wait;           // touch a tile's pixels only once its epochs are >= chain_wait (0: none)
     unsigned long long* started;   // + 1 per block at its start: the next launch's stream gate (nullptr: none)
     uint32_t chain_delay;          // test hook (PT_MI355_TEST_CHAIN_DELAY): ~us a wave sleeps before publishing
+    // camera-hit cache (pt_capi.cpp Sched::cam): what TestSceneTrace returned for each
+    // pixel's camera ray, one record per pixel at [tile * 64 + lane].  The camera ray has no jitter and
+    // the scene is fixed, so the record is the same for every launch of the geometry.  The
+    // continuous-tiles kernels only (render_body_ct); counting instances always trace and, with
+    // PT_CAM_USE, compare (guard PT_G_CAM_RECORD).
+    unsigned long long* cam_cache; // pt_job_tiles() x 64 records (pt_cam_pack); nullptr with PT_CAM_NONE
+    uint32_t cam_mode;             // PtCamMode
 };
 
 // Kernel error words (PtJob::err, PtV4Job::err; reset by the host after it reports them, pt_capi.cpp
@@ -97,6 +106,8 @@ enum PtGuardId : uint32_t {
     PT_G_RECORD = 11,       // a tile's item record slot >= 64
     PT_G_QUEUE_GROUP = 12,  // a queue group counter beyond PT_NQUEUES
     PT_G_CHAIN_WAIT = 13,   // a chained launch polled 2^21 times (>= 2 s) for the previous launch's tile (every build)
+    PT_G_CAM_INDEX = 14,    // a camera-hit cache record outside the geometry's tiles
+    PT_G_CAM_RECORD = 15,   // a counted launch traced a camera hit that differs from its cached record (every build)
 };
 
 // Tile queues: one counter per XCD group, 128 B apart (PT_QUEUE_WORDS u32 per launch).

@@ -1210,10 +1210,12 @@ __device__ __forceinline__ void render_body(const PtJob& job)
 constexpr uint32_t kCtWaveFloats = 2u * 64u * (uint32_t)kChunk * 3u;   // per wave: 12 KiB of f32
 // render_body_ct's per-wave LDS words: the tile being chunked (queue entry, pixel terms of the seed,
 // item-pixel mask, item pixels, next chunk's first frame), A's first frame, D (entry, first frame,
-// frames, item-pixel mask), the tile's folded segments, flags (1 claimed, 2 queue done), chunks
+// frames, item-pixel mask), the tile's folded segments, flags (1 claimed, 2 queue done), chunks, and
+// the launch's camera-hit cache (mode, pointer: kernel arguments that only a tile's start reads --
+// held in scalar registers across the pool loop they cost it spills)
 enum : int {
     kWsTcur, kWsHm, kWsHm1, kWsNh, kWsF0next, kWsF0A, kWsTD, kWsF0D, kWsNfD, kWsHmD, kWsHmD1,
-    kWsTileSeg, kWsSegA, kWsSegD, kWsFlags, kWsChunks, kWsWords
+    kWsTileSeg, kWsSegA, kWsSegD, kWsFlags, kWsChunks, kWsCamMode, kWsCam, kWsCam1, kWsWords
 };
 
 // The env CT kernel runs 6 waves per SIMD: its pool loop fits 80 VGPRs (the spills of that build
@@ -1327,7 +1329,7 @@ __device__ __forceinline__ void render_body_ct(const PtJob& job)
     cam.cam_dist = sc->cam_dist;
     const V3 amb = v3(sc->ambient[0], sc->ambient[1], sc->ambient[2]);
     const V3 zero = v3(0.0f, 0.0f, 0.0f), one = v3(1.0f, 1.0f, 1.0f);
-    unsigned long long n_seg = 0, n_iter = 0, n_samp = 0, n_esc = 0, n_prim = 0, n_fb = 0, n_sky = 0;
+    unsigned long long n_seg = 0, n_iter = 0, n_samp = 0, n_esc = 0, n_prim = 0, n_fb = 0, n_sky = 0, n_cam = 0;
 #if PT_DIAG   // diagnostic build: render_body's per-wave records; tile records from claim to last fold
     const unsigned long long r_birth = __builtin_amdgcn_s_memrealtime();
     unsigned long long n_tiles_diag = 0;
@@ -1368,6 +1370,9 @@ __device__ __forceinline__ void render_body_ct(const PtJob& job)
         ws[kWsFlags] = 0u;
         ws[kWsChunks] = 0u;
         ws[kWsTileSeg] = 0u;
+        ws[kWsCamMode] = job.cam_mode;
+        ws[kWsCam] = (uint32_t)(uintptr_t)job.cam_cache;
+        ws[kWsCam1] = (uint32_t)((uintptr_t)job.cam_cache >> 32);
     }
     // In the pool loop (scalar registers): the chunk contexts -- A hands out items; D has handed out
     // all of its items
@@ -1445,8 +1450,35 @@ __device__ __forceinline__ void render_body_ct(const PtJob& job)
             V3 P1 = zero, N1 = zero;
             int id1 = 0;
             if (valid) {
-                const Hit h = all_sky ? Hit{PT_SUPER_FAR, -1, 0, 0}
-                                      : trace<DemofoxScene, true, QV, true>(s_axis, s_qv, zero, D0);   // :335
+                // the camera-hit cache (pt_kernel.h PtJob::cam_cache): the camera ray's TestSceneTrace result
+                // is the same in every launch of the geometry -- a PT_CAM_USE launch loads it (a sky tile
+                // needs none).  Counting instances trace as ever and compare.
+                const uint32_t ci = pt_entry_tile(tile) * 64u + (uint32_t)lane;
+                const uint32_t cam_mode = ws_ld(kWsCamMode);
+                unsigned long long* const cam_cache =
+                    (unsigned long long*)(uintptr_t)((unsigned long long)ws_ld(kWsCam) | ((unsigned long long)ws_ld(kWsCam1) << 32));
+                const bool cam_ok = cam_mode != PT_CAM_NONE && !all_sky &&
+                                    PT_GUARD(job.err, ci < total_tiles * 64u, PT_G_CAM_INDEX, ci);
+                Hit h{PT_SUPER_FAR, -1, 0, 0};
+                if (!COUNT && cam_ok && cam_mode == PT_CAM_USE) {
+                    const unsigned long long r = cam_cache[ci];
+                    h.id = pt_cam_id(r);
+                    h.best = h.id < 0 ? PT_SUPER_FAR : __builtin_bit_cast(float, pt_cam_best_bits(r));
+                    h.flag = pt_cam_flag(r);
+                    h.fb = pt_cam_fb(r);
+                } else if (!all_sky) {
+                    h = trace<DemofoxScene, true, QV, true>(s_axis, s_qv, zero, D0);   // :335
+                    if (cam_ok) {
+                        const unsigned long long r =
+                            pt_cam_pack(__builtin_bit_cast(uint32_t, h.best), h.best == PT_SUPER_FAR ? -1 : h.id, h.flag, h.fb);
+                        if (!COUNT && cam_mode == PT_CAM_FILL) cam_cache[ci] = r;
+                        if (COUNT && cam_mode == PT_CAM_USE) {
+                            ++n_cam;
+                            if (cam_cache[ci] != r && !(h.best == PT_SUPER_FAR && pt_cam_id(cam_cache[ci]) < 0))
+                                pt_guard_report(job.err, PT_G_CAM_RECORD, ci);
+                        }
+                    }
+                }
                 if (COUNT) ++n_seg, ++n_prim, n_fb += (unsigned long long)h.fb, n_sky += all_sky ? 1ull : 0ull;
                 if (COUNT) n_samp += (unsigned long long)S;
                 V3 c_keep;
@@ -1761,6 +1793,7 @@ __device__ __forceinline__ void render_body_ct(const PtJob& job)
             n_prim += __shfl_xor(n_prim, off, 64);
             n_fb += __shfl_xor(n_fb, off, 64);
             n_sky += __shfl_xor(n_sky, off, 64);
+            n_cam += __shfl_xor(n_cam, off, 64);
         }
         if (lane == 0) {
             atomicAdd(&job.counters[PT_CNT_SEGMENTS], n_seg);
@@ -1770,6 +1803,7 @@ __device__ __forceinline__ void render_body_ct(const PtJob& job)
             atomicAdd(&job.counters[PT_CNT_PRIMARY], n_prim);
             atomicAdd(&job.counters[PT_CNT_FALLBACK], n_fb);
             atomicAdd(&job.counters[PT_CNT_SKY], n_sky);
+            atomicAdd(&job.counters[PT_CNT_CAM_CHECKED], n_cam);
         }
     }
 }

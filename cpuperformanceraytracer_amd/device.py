@@ -110,6 +110,23 @@ def launch_variant(buf, width: int, height: int, *, nframes: int, num_bounces: i
     return {"waves_per_simd": int(w.value), "back_claim_pct": int(b.value)}
 
 
+CAM_CACHE_STATES = ("none", "empty", "filled", "settled")   # PT_CAM_CACHE_*
+
+
+def cam_cache_query(buf, width: int, height: int, *, nframes: int, num_bounces: int, row_start: int = 0,
+                    row_stride: int = 1, nrows: int | None = None, layout: int = N.PT_LAYOUT_INTERLEAVED,
+                    use_env: bool = False, stream=None) -> dict:
+    """The camera-hit cache of this job's geometry and launch length on `stream` (pt_cam_cache_query):
+    its state ("none": such launches trace their camera rays) and the records the device's last
+    count_device launch compared with the hits it traced."""
+    nrows = height if nrows is None else nrows
+    job = _job(buf, width, height, row_start, row_stride, nrows, 1, nframes, num_bounces, layout, use_env)
+    s, c = ctypes.c_int32(0), ctypes.c_uint64(0)
+    N.check(N.load().pt_cam_cache_query(ctypes.byref(job), _stream(stream), ctypes.byref(s), ctypes.byref(c)),
+            "pt_cam_cache_query")
+    return {"state": CAM_CACHE_STATES[int(s.value)], "compared": int(c.value)}
+
+
 def tonemap_device(buf, width: int, nrows: int, pixels, *, layout: int = N.PT_LAYOUT_INTERLEAVED,
                    pixel_format: int = N.PT_PIXEL_RGBA8, stream=None) -> None:
     """The standalone output stage (pt_tonemap_device) on an HBM accumulator of nrows x width pixels

@@ -353,6 +353,19 @@ int pt_render_device_present(const pt_device_job* job, uint32_t* pixels, int32_t
  * geometry's timed launches; *waves = 0 while it is undecided (no scheduled launch timed yet), or for a
  * job that does not run the continuous-tiles pool.  Host state only, no GPU work. */
 int pt_launch_variant(const pt_device_job* job, int32_t* waves, int32_t* back_pct);
+/* The camera-hit cache of `job`'s geometry and launch length on `hip_stream` (its buffer's device): the
+ * diffuse renderers keep, per recurring geometry, what the scene trace returned for every pixel's camera
+ * ray and launches of at least 8 frames load it instead of tracing (8 bytes per pixel, at most 128 MiB;
+ * PT_MI355_CAM_CACHE=0: never).  *state: PT_CAM_CACHE_*.  *compared: the camera hits the device's last
+ * pt_count_device launch traced and compared with their cached records (0: it had no valid cache; a
+ * difference is reported as a kernel error).  Host state only, no GPU work. */
+enum {
+    PT_CAM_CACHE_NONE = 0,    /* this job's launches trace their camera rays */
+    PT_CAM_CACHE_EMPTY = 1,   /* allocated; the next uncounted launch fills it */
+    PT_CAM_CACHE_FILLED = 2,  /* the last launch filled it; the next one (ordered after it) reads it */
+    PT_CAM_CACHE_SETTLED = 3, /* launches read it */
+};
+int pt_cam_cache_query(const pt_device_job* job, void* hip_stream, int32_t* state, uint64_t* compared);
 
 #ifdef __cplusplus
 }
