@@ -2538,6 +2538,31 @@ int pt_v4_render_device(const pt_device_job* dj, void* stream)
     return v4_launch(*dv, j, (hipStream_t)stream, false);
 }
 
+// pt_render_device_present for v4: the continuous-tiles kernel's presenting instances write the pixels
+// with the accumulator (pt_launch_v4); a launch that did not present -- fewer than 8 frames, the
+// per-tile pool, sampling flags without a presenting instance, a tonemap pair other than the default
+// fast ACES / gamma, nothing to render -- is followed by the stand-alone pass over the job's rows.
+int pt_v4_render_device_present(const pt_device_job* dj, uint32_t* pixels, int32_t format, void* stream)
+{
+    int rc;
+    PtV4Job j;
+    Dev* dv = nullptr;
+    DeviceGuard guard;
+    if (!pixels) return fail(PT_EINVAL, "null pixel buffer");
+    if (format != PT_PIXEL_RGBA8 && format != PT_PIXEL_XRGB8) return fail(PT_EINVAL, "unknown pixel format %d", format);
+    if ((rc = ensure_init()) || (rc = v4_device_job(dj, &j)) || (rc = dev_of(dj->buf, &dv))) return rc;
+    j.pix_out = pixels;
+    j.pix_rows = 1;
+    j.pix_xrgb = format == PT_PIXEL_XRGB8;
+    j.pix_fast_tone = g.v4cfg.fast_aces && g.v4cfg.fast_gamma ? 1 : 0;
+    bool presented = false;
+    if ((rc = v4_launch(*dv, j, (hipStream_t)stream, false, &presented)) || presented) return rc;
+    const PtToneJob tj = tone_job(j.buf, j.ncols, j.nrows, j.layout, 0, 0, pixels, format);   // (the v4 config's flags)
+    hipError_t e = pt_launch_tonemap(tj, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PT_EHIP, "tonemap launch failed: %s", hipGetErrorString(e));
+    return PT_OK;
+}
+
 int pt_v4_render_device_chain(const pt_device_job* dj, void* stream)
 {
     int rc;

@@ -84,6 +84,11 @@ struct PtV4Job {
     uint32_t chain_wait;
     unsigned long long* started;
     uint32_t chain_delay;
+    // pix_out's address mode: 1 = job rows, pix_out[k * ncols + (X - col0)] for the job's row k (a
+    // device job's nrows x ncols pixel buffer, pt_v4_render_device_present: the continuous-tiles
+    // kernel's presenting instances); 0 = the full image, as above.  (Last: in the struct's tail
+    // padding, so no other member's kernel-argument offset moved when it was added.)
+    int32_t pix_rows;
 };
 
 // Scene description in AddQuad/Sphere/MaterialToScene order (v4 :1368-1401).

@@ -1041,6 +1041,12 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_OCC void pt_v4_kernel(PtV4Job jo
 // seed terms).  The deferred env misses keep the wave-wide drains of pt_v4_kernel; a queue entry
 // also carries the radiance so far (48 B), and D's fold drains the whole queue first.  The same
 // operations on the same operands: bit-identical to pt_v4_kernel (the -m gpu v4 parity tests).
+// PRESENT: the fused output stage of a device job (pt_v4_render_device_present; job.pix_rows): where
+// a pixel's final accumulator value of the launch is stored -- the fold of its tile's last chunk, or
+// the sky frames when they are the whole launch -- its 8-bit value (pt_tonemap.h, the default fast
+// ACES / gamma) goes to job.pix_out at the job-row address k * ncols + (X - col0), k the job's row:
+// one dword per lane, the lanes of a tile row on neighbouring addresses, as the accumulator's.  Its
+// own instances (launch_t), so the plain kernels' code and register allocation are untouched.
 constexpr uint32_t kV4CtWaveFloats = 2u * 64u * (uint32_t)kChunk * 3u;
 static_assert(kV4CtWaveFloats == 2u * 64u * 8u * 3u, "the slot area is the diffuse pool's (pt_ct_wave_floats)");
 enum : int {   // per-wave LDS words of the events (pt_kernel.hip kWs*)
@@ -1048,7 +1054,7 @@ enum : int {   // per-wave LDS words of the events (pt_kernel.hip kWs*)
     kVwSegA, kVwSegD, kVwFlags, kVwSky, kVwSkyD, kVwWords
 };
 
-template <int ENV, int LAYOUT, bool COUNT, bool DEF, int FEXP, bool DFL = false>
+template <int ENV, int LAYOUT, bool COUNT, bool DEF, int FEXP, bool DFL = false, bool PRESENT = false>
 __global__ __launch_bounds__(64 * kWaves) PT_V4_CT_OCC void pt_v4_ct_kernel(PtV4Job job, PtV4Scene sc)
 {
     __shared__ PtV4Mat s_mat[PT_V4_MAX_OBJECTS];
@@ -1095,6 +1101,15 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_CT_OCC void pt_v4_ct_kernel(PtV4
     const float rW = rcp(W), rH = rcp(H);
     const float cam_dist = 1.0f;   // (as pt_v4_kernel, InitializeCamera :1500)
     unsigned long long n_seg = 0, n_esc = 0, n_slots = 0, n_fb = 0, n_sky = 0;
+    // the fused output stage: pixel column X of job row pr, with its final accumulator value
+    auto present = [&](int X, int pr, const V3& acc) {
+        if constexpr (PRESENT) {
+            const uint32_t lc = (uint32_t)(X - job.col0);
+            const size_t o = (size_t)(uint32_t)pr * (uint32_t)job.ncols + lc;
+            if (PT_GUARD(job.err, lc < (uint32_t)job.ncols && (uint32_t)pr < (uint32_t)job.nrows, PT_G_PIXOUT, o))
+                job.pix_out[o] = pt_tone::pack<true, true>(acc.x, acc.y, acc.z, job.pix_xrgb != 0);
+        }
+    };
 
     constexpr uint32_t kNone = PtTileQueue<kWaves>::kNone;
     {
@@ -1239,6 +1254,7 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_CT_OCC void pt_v4_ct_kernel(PtV4
                 }
                 if (fsky > 0 && valid) pt_px_st3(job.buf, pxb, cs, pi, acc.x, acc.y, acc.z);   // (the pool's first chunk reads it back)
                 if (fsky == S) {   // the whole tile: ~one pool iteration per frame (the schedule's cost)
+                    if (valid) present(X, pr, acc);   // (S >= 1: acc was stored just above)
                     if (rec_cost && lane == 0) pt_record_cost(job.cost, tile, ntiles, 1u + (uint32_t)fsky);
                     if (job.tile_epoch) pt_chain_publish(job.tile_epoch, tile, job.chain_seq, job.chain_delay, lane);
                     continue;
@@ -1298,6 +1314,7 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_CT_OCC void pt_v4_ct_kernel(PtV4
             }
             if (last) {
                 pt_px_st3(job.buf, pxb, cs, pi, acc.x, acc.y, acc.z);
+                present(px, pr, acc);
             } else {
                 s_acc[wv][0][lane] = acc.x;
                 s_acc[wv][1][lane] = acc.y;
@@ -1470,10 +1487,12 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_CT_OCC void pt_v4_ct_kernel(PtV4
 }
 
 template <int ENV, int LAYOUT>
-hipError_t launch_t(const PtV4Job& j, const PtV4Scene& sc, hipStream_t st, bool count, uint32_t* ct_blocks_out)
+hipError_t launch_t(const PtV4Job& j, const PtV4Scene& sc, hipStream_t st, bool count, bool* presented,
+                    uint32_t* ct_blocks_out)
 {
     const int tiles = ((j.ncols + 7) / 8) * ((j.nrows + 7) / 8);
     const dim3 block(64 * kWaves);
+    *presented = false;
     // persistent grid: the resident blocks, at most one tile per wave.  The continuous-tiles kernel
     // when the caller provides its slots for the whole grid and the launch holds >= 4 full chunks
     // (8 frames x tile) per wave, else the per-tile pool kernel.  Measured (round 4, 5-wave CT vs
@@ -1481,15 +1500,18 @@ hipError_t launch_t(const PtV4Job& j, const PtV4Scene& sc, hipStream_t st, bool 
     // 1080p 8 spp 0.3602 vs 0.3589 (6), 1 spp 0.133 vs 0.115 (one item per pixel and chunk: the
     // chunk events, claim and fold, dominate); round 5, the 6-wave CT kernel: 1080p 8 spp (5.3 chunks
     // per wave) 0.3591 vs 0.3602.
-    const auto go = [&](auto kern, auto ct_kern) {
+    const auto go_ct = [&](auto ct_kern) {   // true: the continuous-tiles kernel took the launch
         const long ct_blocks = std::min<long>(pt_resident_blocks(ct_kern, 64 * kWaves), (tiles + kWaves - 1) / kWaves);
         const uint64_t ct_waves = (uint64_t)ct_blocks * kWaves;
-        if (j.ct_slots && ct_waves <= j.ct_waves && j.nframes >= kChunk &&
-            (j.ct_force || (uint64_t)j.nframes * (uint64_t)tiles >= 4ull * kChunk * ct_waves)) {
-            hipLaunchKernelGGL(ct_kern, dim3((unsigned)ct_blocks), block, 0, st, j, sc);
-            if (ct_blocks_out) *ct_blocks_out = (uint32_t)ct_blocks;
-            return;
-        }
+        if (!(j.ct_slots && ct_waves <= j.ct_waves && j.nframes >= kChunk &&
+              (j.ct_force || (uint64_t)j.nframes * (uint64_t)tiles >= 4ull * kChunk * ct_waves)))
+            return false;
+        hipLaunchKernelGGL(ct_kern, dim3((unsigned)ct_blocks), block, 0, st, j, sc);
+        if (ct_blocks_out) *ct_blocks_out = (uint32_t)ct_blocks;
+        return true;
+    };
+    const auto go = [&](auto kern, auto ct_kern) {
+        if (go_ct(ct_kern)) return;
         const long blocks = std::min<long>(pt_resident_blocks(kern, 64 * kWaves), (tiles + kWaves - 1) / kWaves);
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), block, 0, st, j, sc);
     };
@@ -1498,6 +1520,18 @@ hipError_t launch_t(const PtV4Job& j, const PtV4Scene& sc, hipStream_t st, bool 
             auto k = pt_v4_kernel<ENV, LAYOUT, false, true, 1, true, true>;
             const long blocks = std::min<long>(pt_resident_blocks(k, 64 * kWaves), (tiles + kWaves - 1) / kWaves);
             hipLaunchKernelGGL(k, dim3((unsigned)blocks), block, 0, st, j, sc);
+            *presented = true;
+            return hipGetLastError();
+        }
+    } else if (j.pix_out && !count) {
+        // the presenting instances of a device job (pt_launch_v4: job-row pixels, fast exp, the default
+        // tonemap pair): the continuous-tiles twins of the default scene's default-flags instance and
+        // of the generic scene's -- a launch the continuous-tiles kernel does not take renders plain
+        // below and the caller converts (*presented stays false)
+        const bool took = j.default_scene ? go_ct(pt_v4_ct_kernel<ENV, LAYOUT, false, true, 1, true, true>)
+                                          : go_ct(pt_v4_ct_kernel<ENV, LAYOUT, false, false, 1, false, true>);
+        if (took) {
+            *presented = true;
             return hipGetLastError();
         }
     }
@@ -1533,12 +1567,12 @@ hipError_t launch_t(const PtV4Job& j, const PtV4Scene& sc, hipStream_t st, bool 
 }
 
 template <int ENV>
-hipError_t launch_env(const PtV4Job& j, const PtV4Scene& sc, hipStream_t st, bool count, uint32_t* ct_blocks)
+hipError_t launch_env(const PtV4Job& j, const PtV4Scene& sc, hipStream_t st, bool count, bool* presented, uint32_t* ct_blocks)
 {
     switch (j.layout) {
-        case PT_LAYOUT_INTERLEAVED: return launch_t<ENV, PT_LAYOUT_INTERLEAVED>(j, sc, st, count, ct_blocks);
-        case PT_LAYOUT_PLANAR8: return launch_t<ENV, PT_LAYOUT_PLANAR8>(j, sc, st, count, ct_blocks);
-        case PT_LAYOUT_TILED_PLANAR8: return launch_t<ENV, PT_LAYOUT_TILED_PLANAR8>(j, sc, st, count, ct_blocks);
+        case PT_LAYOUT_INTERLEAVED: return launch_t<ENV, PT_LAYOUT_INTERLEAVED>(j, sc, st, count, presented, ct_blocks);
+        case PT_LAYOUT_PLANAR8: return launch_t<ENV, PT_LAYOUT_PLANAR8>(j, sc, st, count, presented, ct_blocks);
+        case PT_LAYOUT_TILED_PLANAR8: return launch_t<ENV, PT_LAYOUT_TILED_PLANAR8>(j, sc, st, count, presented, ct_blocks);
         default: return hipErrorInvalidValue;
     }
 }
@@ -1554,25 +1588,33 @@ hipError_t pt_v4_set_chain_polls(uint32_t polls)
 hipError_t pt_launch_v4(const PtV4Job& j_in, const PtV4Scene& sc, hipStream_t st, bool count, bool* presented,
                         uint32_t* ct_blocks)
 {
-    if (presented) *presented = false;
+    bool pres = false;
+    if (!presented) presented = &pres;
+    *presented = false;
     if (ct_blocks) *ct_blocks = 0;
     if (j_in.ncols <= 0 || j_in.nrows <= 0 || j_in.nframes <= 0) return hipSuccess;
-    // the fused output stage (j.pix_out) runs in the presenting instances only: the drop-in's calls
-    // (DemofoxRenderOptV4: the tiled layout, one frame -- the per-tile pool kernel), the default scene
-    // and sampling flags, fast exp, and the default fast ACES / gamma
+    // the fused output stage (j.pix_out) runs in the presenting instances only, uncounted, with fast
+    // exp and the default fast ACES / gamma:
+    //  - the drop-in's calls (DemofoxRenderOptV4: the tiled layout, one frame -- the per-tile pool
+    //    kernel, full-image pixel rows), the default scene and sampling flags;
+    //  - device jobs (pt_v4_render_device_present: a row layout, job-row pixels, pix_rows) that the
+    //    continuous-tiles kernel takes (launch_t decides: *presented), the default scene with the
+    //    default sampling flags or a generic scene.
     PtV4Job j = j_in;
-    if (j.pix_out && !(j.layout == PT_LAYOUT_TILED_PLANAR8 && j.nframes < kChunk && j.default_scene && j.fast_exp &&
-                       j.random_jitter && j.rejection && j.pix_fast_tone && !count))
+    const bool tiled = j.layout == PT_LAYOUT_TILED_PLANAR8;
+    const bool tone = j.fast_exp && j.pix_fast_tone && !count;
+    const bool dflt = j.default_scene && j.random_jitter && j.rejection;
+    if (j.pix_out && !(tone && (j.pix_rows ? !tiled && j.nframes >= kChunk && (dflt || !j.default_scene)
+                                           : tiled && j.nframes < kChunk && dflt)))
         j.pix_out = nullptr;
-    if (presented) *presented = j.pix_out != nullptr;
     if (sc.nquads < 0 || sc.nspheres < 0 || sc.nquads + sc.nspheres > PT_V4_MAX_OBJECTS) return hipErrorInvalidValue;
     if (j.env_mode != PT_V4_ENV_NONE_ && (!j.env || j.env_w <= 0 || j.env_h <= 0)) return hipErrorInvalidValue;
     if (count && !j.counters) return hipErrorInvalidValue;
     if (!j.queue || (j.order && (!j.units || !j.nunits))) return hipErrorInvalidValue;
     switch (j.env_mode) {
-        case PT_V4_ENV_NONE_: return launch_env<PT_V4_ENV_NONE_>(j, sc, st, count, ct_blocks);
-        case PT_V4_ENV_EQUIRECT_: return launch_env<PT_V4_ENV_EQUIRECT_>(j, sc, st, count, ct_blocks);
-        case PT_V4_ENV_CUBEMAP_: return launch_env<PT_V4_ENV_CUBEMAP_>(j, sc, st, count, ct_blocks);
+        case PT_V4_ENV_NONE_: return launch_env<PT_V4_ENV_NONE_>(j, sc, st, count, presented, ct_blocks);
+        case PT_V4_ENV_EQUIRECT_: return launch_env<PT_V4_ENV_EQUIRECT_>(j, sc, st, count, presented, ct_blocks);
+        case PT_V4_ENV_CUBEMAP_: return launch_env<PT_V4_ENV_CUBEMAP_>(j, sc, st, count, presented, ct_blocks);
         default: return hipErrorInvalidValue;
     }
 }

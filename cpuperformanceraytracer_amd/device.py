@@ -173,13 +173,11 @@ class JobLauncher:
         L = N.load()
         self._ref = ctypes.byref(self.job)
         self._stream = _stream(stream)
-        if pixels is not None:   # the fused output stage (pt_render_device_present)
-            if v4:
-                raise N.PtError(N.PT_EINVAL, "JobLauncher", "pixels: diffuse renderer only")
+        if pixels is not None:   # the fused output stage (pt_render_device_present / pt_v4_render_device_present)
             _check_pixels(pixels, width * nrows, buf)
             self._pixels = pixels
-            fn, args = L.pt_render_device_present, (self._ref, pixels.data_ptr(), pixel_format, self._stream)
-            self._what = "pt_render_device_present"
+            self._what = "pt_v4_render_device_present" if v4 else "pt_render_device_present"
+            fn, args = getattr(L, self._what), (self._ref, pixels.data_ptr(), pixel_format, self._stream)
         else:
             # chain: pt_render_device_chain / pt_v4_render_device_chain, consecutive launches overlap
             self._what = ("pt_v4_render_device" if v4 else "pt_render_device") + ("_chain" if chain else "")
@@ -210,6 +208,24 @@ def render_v4_device(buf, width: int, height: int, *, frame_first: int, nframes:
     nrows = height if nrows is None else nrows
     job = _job(buf, width, height, row_start, row_stride, nrows, frame_first, nframes, num_bounces, layout, use_env)
     N.check(N.load().pt_v4_render_device(ctypes.byref(job), _stream(stream)), "pt_v4_render_device")
+
+
+def render_v4_device_present(buf, pixels, width: int, height: int, *, frame_first: int, nframes: int,
+                             num_bounces: int = 8, row_start: int = 0, row_stride: int = 1, nrows: int | None = None,
+                             layout: int = N.PT_LAYOUT_INTERLEAVED, use_env: bool = False,
+                             pixel_format: int = N.PT_PIXEL_RGBA8, stream=None) -> None:
+    """render_v4_device with the output stage fused into the render (pt_v4_render_device_present): also
+    writes the job's rows as packed 8-bit pixels (nrows x width int32/uint32 device tensor `pixels`,
+    row k = the job's row k; PT_PIXEL_RGBA8 = OutputToFile, PT_PIXEL_XRGB8 = OutputToScreen) with the
+    tonemap flags of renderer.v4_config -- equal to render_v4_device followed by tonemap_device on
+    those rows.  Launches of 8 or more frames that run the continuous-tiles kernel with the default
+    tonemap flags write the pixels in the render kernel; every other launch converts in a second pass
+    on the same stream.  Asynchronous on `stream`."""
+    nrows = height if nrows is None else nrows
+    job = _job(buf, width, height, row_start, row_stride, nrows, frame_first, nframes, num_bounces, layout, use_env)
+    _check_pixels(pixels, width * nrows, buf)
+    N.check(N.load().pt_v4_render_device_present(ctypes.byref(job), pixels.data_ptr(), pixel_format, _stream(stream)),
+            "pt_v4_render_device_present")
 
 
 def count_v4_device(buf, width: int, height: int, *, frame_first: int, nframes: int, num_bounces: int = 8,

@@ -296,6 +296,18 @@ int pt_v4_render_device(const pt_device_job* job, void* hip_stream);
 /* pt_v4_render_device for consecutive launches of one geometry: may overlap the previous chained launch
  * of that geometry on this stream, same result (the contract of pt_render_device_chain) */
 int pt_v4_render_device_chain(const pt_device_job* job, void* hip_stream);
+/* pt_v4_render_device with the output stage fused into the render -- pt_render_device_present (below)
+ * for the v4 renderer, the reference's OutputToScreen right after RenderTile (v4 :1562-1564).  The
+ * accumulator ends bit for bit as pt_v4_render_device leaves it; `pixels` (device memory on the job's
+ * device, nrows x width u32, row k = the job's row k -- not the full image) receives every pixel's
+ * packed 8-bit value (PT_PIXEL_*), equal to pt_tonemap_device on that accumulator with the
+ * pt_v4_config's fast_aces / fast_gamma.  A launch of 8 or more frames that runs the continuous-tiles
+ * kernel with the default tonemap pair (1, 1) -- the default scene with the default sampling flags,
+ * or an edited scene, fast_exp 1 -- writes the pixels in the render kernel; every other launch
+ * (fewer frames, PT_MI355_NO_CT=1, other flags, nframes == 0: nothing rendered) renders plain and
+ * converts in a second pass on hip_stream.  Not chained: a plain launch, it ends a live chain.
+ * NULL pixels or an unknown format: PT_EINVAL.  Async on hip_stream. */
+int pt_v4_render_device_present(const pt_device_job* job, uint32_t* pixels, int32_t format, void* hip_stream);
 int pt_v4_count_device(const pt_device_job* job, void* hip_stream, pt_work_counts* out);   /* sync */
 
 /* --- tile work queue: the host tile scheduler, on the GPU ------------------------
