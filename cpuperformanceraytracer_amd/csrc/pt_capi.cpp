@@ -19,6 +19,7 @@
 // the host buffer); transfers move only the owned rows (pitched 2D copies).
 #include "pt_kernel.h"
 #include "pt_guard.h"
+#include "pt_launch_plan.h"
 #include "pt_output.h"
 #include "pt_v4.h"
 #include "../../include/pt_mi355.h"
@@ -41,7 +42,7 @@ struct SchedKey {
     int32_t width = 0, height = 0, col0 = 0, ncols = 0, row_start = 0, row_stride = 0, nrows = 0, bounces = 0;
     const float* env = nullptr;
     uint32_t ntiles = 0;
-    uint32_t split = 0;   // the schedule builder's split factor (launch(): one-chunk launches only)
+    uint32_t split = 0;   // the schedule builder's split factor (pt_plan_split: one-chunk launches only)
     bool operator==(const SchedKey& o) const
     {
         return kind == o.kind && width == o.width && height == o.height && col0 == o.col0 && ncols == o.ncols &&
@@ -57,6 +58,7 @@ struct Sched {
     uint32_t* order = nullptr;
     uint32_t* units = nullptr;    // 2 ntiles + 2 words: run starts, then the run count (cost: 2 ntiles words,
                                   // order: up to 2 ntiles entries -- split tiles, pt_tile_queue.h)
+    uint32_t* nunits() const { return units + 2 * (size_t)key.ntiles + 1; }
     bool have_cost = false;
     bool built = false;           // order/units hold a schedule
     unsigned long long launches = 0;
@@ -79,15 +81,10 @@ struct Sched {
     // at most as long as its Sched.  nullptr: none (yet); cam_off: the allocation failed, never again.
     unsigned long long* cam = nullptr;
     bool cam_off = false;
-    // kCamEmpty; kCamFilled: the geometry's last launch filled it (the next launch is stream-ordered
-    // after it: a chained one restarts); kCamSettled: every later launch may read it
-    uint8_t cam_state = 0;
+    uint8_t cam_state = kCamEmpty;   // (pt_launch_plan.h)
 };
-enum : uint8_t { kCamEmpty = 0, kCamFilled = 1, kCamSettled = 2 };
-constexpr uint32_t kTuneRounds = 3;   // rounds of the palindromic arm order timed; the first is discarded
 constexpr int kSchedSlots = 16;
 constexpr int kBands = 4;   // PT_FLAG_PIN_HOST: row bands of a pipelined frame
-constexpr uint32_t kSchedMinTiles = 512;   // smaller jobs (e.g. one RenderTile) are not scheduled
 constexpr unsigned kQueueRing = 256;       // tile-queue ring slots (reuse across streams is event-ordered)
 // launches per schedule build (g.sched_rebuild; PT_MI355_SCHED_REBUILD): 256 -- a build restarts the
 // chained overlap and costs a one-workgroup kernel (~57 us at 1080p); 3-round A/B of chained steps vs 64
@@ -532,27 +529,8 @@ PtJob base_job(float* buf, int32_t w, int32_t h)
     j.frame_first = g.frame + 1;
     j.nframes = g.cfg.samples_per_frame;
     j.num_bounces = g.cfg.num_bounces;
-    j.env = nullptr;
-    j.env_w = j.env_h = 0;
-    j.counters = nullptr;
-    j.order = nullptr;
-    j.units = nullptr;
-    j.nunits = nullptr;
-    j.cost = nullptr;
-    j.err = nullptr;
     j.guard_cap = g.ring_guard_cap;
-    j.ct_slots = nullptr;
-    j.ct_waves = 0;
-    j.ct_back_pct = 0;   // (launch(): launches of <= 16 frames)
-    j.ct_wide = 0;
-    j.scene = nullptr;
-    j.tile_epoch = nullptr;
-    j.chain_seq = 0;
-    j.chain_wait = 0;
-    j.started = nullptr;
-    j.cam_cache = nullptr;
-    j.cam_mode = PT_CAM_NONE;
-    return j;
+    return j;   // (every other field null or zero: the caller, launch_with, prepare and launch_chain set them)
 }
 
 void free_sched(Sched& s)
@@ -567,63 +545,30 @@ void free_sched(Sched& s)
     s = Sched{};
 }
 
-SchedKey sched_key(const PtJob& j)
+// A schedule's key: the nine members the renderers share, and what differs -- the kind, the tile count
+// and the split factor.  v4 takes whole tiles: its per-tile kernel runs launches of < 8 frames (and
+// PT_MI355_NO_CT=1), and split tiles measured slower on the continuous-tiles one (0.3666 vs 0.3633 ms at
+// 1080p 8 spp).
+template <typename Job>
+SchedKey sched_key(const Job& j, int32_t kind, uint32_t ntiles, uint32_t split)   // (in SchedKey's member order)
 {
-    SchedKey k;
-    k.kind = 0;
-    k.width = j.width;
-    k.height = j.height;
-    k.col0 = j.col0;
-    k.ncols = j.ncols;
-    k.row_start = j.row_start;
-    k.row_stride = j.row_stride;
-    k.nrows = j.nrows;
-    k.bounces = j.num_bounces;
-    k.env = j.env;
-    k.ntiles = pt_job_tiles(j);
-    return k;
+    return {kind, j.width, j.height, j.col0, j.ncols, j.row_start, j.row_stride, j.nrows, j.num_bounces, j.env, ntiles, split};
 }
-
+SchedKey sched_key(const PtJob& j) { return sched_key(j, 0, pt_job_tiles(j), pt_plan_split(j.nframes, g.split)); }
 SchedKey sched_key(const PtV4Job& j)
 {
-    SchedKey k;
-    k.kind = 1 + j.env_mode;
-    k.width = j.width;
-    k.height = j.height;
-    k.col0 = j.col0;
-    k.ncols = j.ncols;
-    k.row_start = j.row_start;
-    k.row_stride = j.row_stride;
-    k.nrows = j.nrows;
-    k.bounces = j.num_bounces;
-    k.env = j.env;
-    k.ntiles = (uint32_t)((j.ncols + 7) / 8) * (uint32_t)((j.nrows + 7) / 8);
-    return k;
+    return sched_key(j, 1 + j.env_mode, (uint32_t)((j.ncols + 7) / 8) * (uint32_t)((j.nrows + 7) / 8), 0u);
 }
 
-bool cam_cache_wanted(const SchedKey& key) { return pt_cam_cache_wanted(g.cam_cache, key.kind, key.ntiles); }
-
-// Launches of fewer frames neither fill nor use a cache, and move no cache state.  A tile of such a
-// launch carries few items, and the record load at the tile's start -- a dependent HBM / MALL access
-// right after the claim's atomic -- then costs more than the coherent camera trace it replaces.
-// Measured at 1920 x 1080, parent vs cache for every length (profiles/camcache): 1 frame per launch
-// 0.1142 -> 0.1168 ms (+2.3 %), 8 frames 0.2198 -> 0.2169 (-1.3 %), 16 (env) and 64 (4K) -0.5 %.  The
-// bound is the shortest length measured to gain, one whole chunk (kChunk, pt_kernel.hip).
-constexpr int32_t kCamMinFrames = 8;
 bool cam_launch_qualifies(const Sched& s, int32_t nframes)
 {
-    return !s.cam_off && nframes >= kCamMinFrames && cam_cache_wanted(s.key);
-}
-// A chained launch may continue the overlap (launch_chain) unless it would fill the cache or read
-// records that a launch it may overlap is still writing.
-bool cam_chain_may_continue(const Sched& s, int32_t nframes)
-{
-    return !cam_launch_qualifies(s, nframes) || (s.cam && s.cam_state == kCamSettled);
+    return pt_cam_launch_qualifies(s.cam_off, nframes, pt_cam_cache_wanted(g.cam_cache, s.key.kind, s.key.ntiles));
 }
 
 // The camera-hit cache fields of a launch of `s`'s geometry on `st` that is stream-ordered after the
-// geometry's earlier launches (every launch but a continuing chained one).  A counted launch never
-// fills: it traces the camera rays for its counters, and compares them with a valid cache.
+// geometry's earlier launches -- or a continuing chained one, which neither fills nor settles a cache
+// (pt_cam_chain_may_continue).  A counted launch never fills: it traces the camera rays for its counters,
+// and compares them with a valid cache.
 void cam_cache_job(Sched* s, PtJob& j, bool count, hipStream_t st)
 {
     j.cam_cache = nullptr;
@@ -703,6 +648,7 @@ struct LaunchSched {
     uint32_t* cost = nullptr;
     Sched* sched = nullptr;   // with a built schedule
     Sched* geo = nullptr;     // the geometry's Sched, built or not
+    void use(Sched& s) { sched = &s, order = s.order, units = s.units, nunits = s.nunits(); }   // (s is built)
 };
 // Order `st` after every chained launch of the device and end the live chain (launch_chain): a
 // launch that is not a continuing chained one may use what the chained launches use -- the slot
@@ -722,42 +668,32 @@ int chain_join(Dev& dv, hipStream_t st)
     return PT_OK;
 }
 
-// split: the schedule builder's tile split factor (pt_launch_schedule; 0: whole tiles).  *sched_st: the
-// stream that identifies the geometry's schedule (launch_chain: the caller's stream, which may be the
-// null stream; nullptr: st).
-int use_sched(Dev& dv, const SchedKey& key, hipStream_t st, LaunchSched* ls, uint32_t split,
-              const hipStream_t* sched_st = nullptr)
+// key.split: the schedule builder's tile split factor (pt_launch_schedule; 0: whole tiles).  *sched_st:
+// the stream that identifies the geometry's schedule (launch_chain: the caller's stream, which may be
+// the null stream; nullptr: st).
+int use_sched(Dev& dv, const SchedKey& key, hipStream_t st, LaunchSched* ls, const hipStream_t* sched_st = nullptr)
 {
     *ls = LaunchSched{};
     int rc;
     if ((rc = chain_join(dv, st))) return rc;
     if (Sched* s = find_sched(dv, key, sched_st ? *sched_st : st)) {
         ls->geo = s;
-        // (re)build the schedule from the last launch's costs on the 2nd launch of a geometry and
-        // then every g.sched_rebuild launches (the costs of a fixed view barely change; the builder
-        // is a one-workgroup kernel of ~57 us at 1080p)
-        if (s->have_cost && (!s->built || s->launches % g.sched_rebuild == 0)) {
+        const PtSchedStep step = pt_plan_sched_step(s->have_cost, s->built, s->launches, g.sched_rebuild);
+        if (step.builds) {
             // units of twice the adaptive cost for the diffuse kernels' continuous-tiles pool, whose
             // lanes no longer idle in a unit's tail while the dequeues still cost (A/B, 60 launches:
             // 1080p 8 spp 0.2497 vs 0.2525 ms, env 16 spp 0.4911 vs 0.4961, 4K 8 spp 0.8185 vs 0.8202;
             // 3x: 0.2513 / 0.4965 / 0.8356)
             const uint32_t unit_mult = key.kind == 0 && !g.no_ct ? g.unit_mult : 1u;
-            hipError_t e = pt_launch_schedule(s->cost, s->order, s->units, s->units + 2 * s->key.ntiles + 1, s->key.ntiles,
-                                              split, unit_mult, st, dv.derr);
+            hipError_t e = pt_launch_schedule(s->cost, s->order, s->units, s->nunits(), s->key.ntiles, key.split, unit_mult,
+                                              st, dv.derr);
             if (e != hipSuccess) return fail(PT_EHIP, "schedule launch failed: %s", hipGetErrorString(e));
             s->built = true;
             if (g.test_bad_entry >= 0 && (uint32_t)g.test_bad_entry < 2u * s->key.ntiles)   // (test hook, below)
                 HIP_TRY(hipMemsetAsync(s->order + g.test_bad_entry, 0xff, sizeof(uint32_t), st));
         }
-        if (s->built) {
-            ls->sched = s;
-            ls->order = s->order;
-            ls->units = s->units;
-            ls->nunits = s->units + 2 * s->key.ntiles + 1;
-        }
-        // the kernel records the tiles' costs only when the next launch builds from them (one 4-B
-        // store per tile is a 32-B HBM write: ~1 MB per 1080p launch otherwise)
-        if (!s->built || (s->launches + 1) % g.sched_rebuild == 0) {
+        if (s->built) ls->use(*s);
+        if (step.records) {
             ls->cost = s->cost;
             s->have_cost = true;
         }
@@ -834,28 +770,8 @@ int use_ct_slots(Dev& dv, const LaunchSched& ls, hipStream_t st, float** slots, 
     return PT_OK;
 }
 
-// The launch variant of a continuous-tiles launch (diffuse and env kernels): PtJob::ct_wide (5 or 6 waves per SIMD) and
-// PtJob::ct_back_pct.  PT_MI355_CT_WAVES=5|6 fixes the occupancy (and the env share); by default (0) the geometry's first
-// scheduled launches time the ARMS and the fastest is kept (per stream: a geometry's Sched):
-//   arm 0: 5 waves, arm 1: 6 waves -- each with the default back-claim share (20 %) -- and, for
-//   launches that take back claims (<= 16 frames) unless PT_MI355_BACK is given, arm 2: 6 waves with
-//   kBackWide % of the grid claiming from the back.  Measured (profiles/r05/r05i_back_sweep_ab.jsonl,
-//   r05h_back_ab.jsonl): at 6 waves 45 % gave 1080p 8 spp 0.2392 vs 0.2440 ms and 4K 8 spp 0.8015 vs
-//   0.8395 (55-90 %: 0.249 / 0.80), but 720p 0.1490 vs 0.1462 and, at 5 waves, 1080p 0.2526 vs 0.2488 --
-//   so it is one more timed arm, not a new default.
-// The env kernel has one occupancy (PT_ENV_WAVES); its arms, for launches that take back claims unless
-//   PT_MI355_BACK is given, are the back-claim shares 20 (default), 33 and 45 %: measured
-//   (profiles/r05/r05k_env_back_ab.jsonl) 1080p 8 frames 0.2786 / 0.2809 / 0.2738 ms, 16 frames
-//   0.4821 / 0.4770 / 0.4885 -- the best share depends on the launch, as for the diffuse kernel.
-// The arms are timed in a palindromic order (ABBA, ABCCBA), three rounds of which the first is not
-// counted: the clocks of a fresh process ramp up over its first launches -- a plain
-// alternation favoured the later arm, and one round of ABCCBA still picked 5 waves for 4K 8 spp in
-// one of two runs (0.8242 vs 0.8023 ms, profiles/r05/r05j_timing3_ab.jsonl).  Until the pick: 6
-// waves for launches of several chunks (ahead at 16 and 64 spp), 5 for one-chunk launches.  No pixel
-// depends on the variant (tests/test_gpu_regime.py forces grid changes).
-// *tev: the event pair to record around this launch while it is timed.
-constexpr uint32_t kBackWide = 45;
-constexpr uint32_t kEnvBack[3] = {0, 33, 45};   // env arms 1, 2 (arm 0: the default share)
+// The launch variant of a continuous-tiles launch (PtJob::ct_wide, ct_back_pct; the arms and why:
+// pt_launch_plan.h): here, the events and the state.  *tev: the pair to record around a timed launch.
 int ct_occupancy(const LaunchSched& ls, PtJob& j, hipEvent_t** tev, bool count)
 {
     *tev = nullptr;
@@ -865,25 +781,21 @@ int ct_occupancy(const LaunchSched& ls, PtJob& j, hipEvent_t** tev, bool count)
         return PT_OK;
     }
     Sched* s = ls.sched;
-    const bool env_arms = j.env && j.ct_back_pct != 0 && !g.back_set;
-    if (g.ct_waves || !j.ct_slots || !s || (j.env && !env_arms)) return PT_OK;
+    const bool env = j.env != nullptr;
+    if (g.ct_waves || !j.ct_slots || !s || (env && !pt_plan_env_arms(env, j.ct_back_pct, g.back_set))) return PT_OK;
     const auto apply = [&](int arm) {
-        if (j.env) {   // (one occupancy: the arms are back-claim shares)
-            if (arm) j.ct_back_pct = kEnvBack[arm];
-            return;
-        }
-        j.ct_wide = arm != 0 ? 1u : 0u;
-        if (arm == 2 && j.ct_back_pct != 0) j.ct_back_pct = kBackWide;   // (launches that take back claims)
+        const PtVariant v = pt_plan_variant(env, arm, j.ct_back_pct, g.back_set);
+        j.ct_wide = v.wide;
+        j.ct_back_pct = v.back_pct;
     };
     // only uncounted launches of the first timed launch's length are timed: a counted launch (the
     // bench's work-count pass) or one of another length sharing the geometry's schedule would bias the
     // arms' sums; they run the interim choice below.  The first timed launch fixes the
     // arms (and the length).
     const bool timeable = !count && (s->tune_nframes == 0 || s->tune_nframes == j.nframes);
-    if (!s->narms && timeable) s->narms = (j.env || (j.ct_back_pct != 0 && !g.back_set)) ? 3u : 2u;
-    const uint32_t per_round = s->narms == 3 ? 6u : 4u, nt = s->narms ? kTuneRounds * per_round : 0u;
-    static constexpr int kOrder3[6] = {0, 1, 2, 2, 1, 0};
-    const auto arm_of = [&](uint32_t t) { return s->narms == 3 ? kOrder3[t % 6] : (int)((t ^ (t >> 1)) & 1u); };
+    if (!s->narms && timeable) s->narms = pt_plan_narms(env, j.ct_back_pct, g.back_set);
+    const uint32_t per_round = pt_plan_round_launches(s->narms), nt = pt_plan_tune_launches(s->narms);
+    const auto arm_of = [&](uint32_t t) { return pt_plan_arm_of(s->narms, t); };
     if (s->wide >= 0) {
         apply(s->wide);
     } else if (s->tuned < nt && timeable) {
@@ -907,22 +819,52 @@ int ct_occupancy(const LaunchSched& ls, PtJob& j, hipEvent_t** tev, bool count)
         apply(best);
     } else {
         (void)hipGetLastError();   // (hipErrorNotReady: the timed launches are still running)
-        apply(j.env || j.nframes <= 8 ? 0 : 1);
+        apply(pt_plan_interim_arm(env, j.nframes));
     }
     return PT_OK;
 }
 
-// *ct_blocks (optional): the continuous-tiles grid launched (0: none); sched_st: see use_sched.
-int launch(Dev& dv, PtJob j, hipStream_t st, bool count, uint32_t* ct_blocks = nullptr, const hipStream_t* sched_st = nullptr)
+// What differs between the renderers in a launch, besides the schedule's key: what the device, the
+// configuration and the launch variant set in the job (prepare), and the kernel entry point (enqueue).
+// The diffuse kernels time their arms on a geometry's first launches and cache camera hits; v4 has one
+// variant and no cache.  cont: a continuing chained launch (launch_chain), which takes the chained share.
+int prepare(const Dev& dv, const LaunchSched& ls, PtJob& j, hipStream_t st, bool count, bool cont, hipEvent_t** tev)
 {
-    LaunchSched ls;
     int rc;
-    // split tiles: launches of one 8-frame chunk (a tile's half of several chunks is a short chunk
-    // each, and the pool's two chunk contexts then wait on each other: 1080p 16 spp 0.452 vs 0.437 ms)
-    SchedKey key = sched_key(j);
-    key.split = j.nframes <= 8 ? g.split : 0u;
-    if ((rc = use_dev(dv)) || (rc = use_sched(dv, key, st, &ls, key.split, sched_st))) return rc;
     j.scene = dv.dscene;
+    j.ct_back_pct = pt_plan_back(j.nframes, g.ct_back_pct);
+    if ((rc = ct_occupancy(ls, j, tev, count))) return rc;
+    if (cont) j.ct_back_pct = pt_plan_chain_back(j.env != nullptr, j.ct_back_pct, g.back_set);
+    cam_cache_job(ls.geo, j, count, st);
+    return PT_OK;
+}
+int prepare(const Dev& dv, const LaunchSched&, PtV4Job& j, hipStream_t, bool, bool cont, hipEvent_t**)
+{
+    if (j.env_mode != PT_V4_ENV_NONE) j.env = dv.denv;
+    j.ct_force = g.v4_ct_force;
+    j.ct_back_pct = cont ? pt_plan_chain_back_v4(j.nframes, g.ct_back_pct, g.back_set) : pt_plan_back(j.nframes, g.ct_back_pct);
+    return PT_OK;
+}
+int enqueue(const LaunchSched& ls, const PtJob& j, hipStream_t st, bool count, bool*, uint32_t* n)
+{
+    hipError_t e = pt_launch_render(j, st, count, n);
+    if (e != hipSuccess) return fail(PT_EHIP, "render launch failed: %s", hipGetErrorString(e));
+    if (j.cam_mode == PT_CAM_FILL && *n) ls.geo->cam_state = kCamFilled;   // (a continuous-tiles kernel ran)
+    return PT_OK;
+}
+int enqueue(const LaunchSched&, const PtV4Job& j, hipStream_t st, bool count, bool* presented, uint32_t* n)
+{
+    hipError_t e = pt_launch_v4(j, g.v4scene, st, count, presented, n);
+    return e == hipSuccess ? PT_OK : fail(PT_EHIP, "v4 render launch failed: %s", hipGetErrorString(e));
+}
+
+// What plain and continuing chained launches share: the job `j`, whose slot area is set, takes the
+// schedule and queue fields of `ls` (PtJob and PtV4Job name them alike) and is enqueued on `st`, between
+// ct_occupancy's event pair if it is timed.  *blocks: the continuous-tiles grid launched (0: none).
+template <typename Job>
+int launch_with(Dev& dv, Job& j, const LaunchSched& ls, hipStream_t st, bool count, bool cont, bool* presented, uint32_t* blocks)
+{
+    int rc;
     j.queue = ls.queue;
     j.queue_next = ls.queue_next;
     j.order = ls.order;
@@ -930,23 +872,29 @@ int launch(Dev& dv, PtJob j, hipStream_t st, bool count, uint32_t* ct_blocks = n
     j.nunits = ls.nunits;
     j.cost = ls.cost;
     j.err = dv.derr;
-    if ((rc = use_ct_slots(dv, ls, st, &j.ct_slots, &j.ct_waves))) return rc;
-    // the last-dispatched fifth of the grid (each CU's 5th block, the slowest under the SQ's
-    // oldest-first issue) claims the cheapest units, for launches of <= 16 frames, whose end is a
-    // large part of them (A/B, scripts/gpu_ab.sh, 20 % vs none: 1080p 8 spp 0.2533 vs 0.2561 ms,
-    // env 16 spp 0.4967 vs 0.5030, 4K 8 spp 0.8217 vs 0.8309; 4K 64 spp 5.913 vs 5.763: not there)
-    j.ct_back_pct = j.nframes <= 16 ? g.ct_back_pct : 0u;
     hipEvent_t* tev = nullptr;
-    if ((rc = ct_occupancy(ls, j, &tev, count))) return rc;
-    cam_cache_job(ls.geo, j, count, st);
-    uint32_t blocks = 0;
+    if ((rc = prepare(dv, ls, j, st, count, cont, &tev))) return rc;
     if (tev) HIP_TRY(hipEventRecord(tev[0], st));
-    hipError_t e = pt_launch_render(j, st, count, &blocks);
-    if (e != hipSuccess) return fail(PT_EHIP, "render launch failed: %s", hipGetErrorString(e));
-    if (ct_blocks) *ct_blocks = blocks;
-    if (j.cam_mode == PT_CAM_FILL && blocks) ls.geo->cam_state = kCamFilled;   // (a continuous-tiles kernel ran)
+    if ((rc = enqueue(ls, j, st, count, presented, blocks))) return rc;
     if (tev) HIP_TRY(hipEventRecord(tev[1], st));
-    return queue_done(dv, ls.slot, st, j.ncols > 0 && j.nrows > 0 && j.nframes > 0);   // (pt_launch_render's early return)
+    return PT_OK;
+}
+
+// A plain launch of either renderer.  *ct_blocks: as launch_with's; sched_st: see use_sched; *presented: pt_launch_v4's
+// (all optional; the v4 pool's slots per wave: pt_v4_ct_wave_floats() <= pt_ct_wave_floats(), pt_v4.hip)
+template <typename Job>
+int launch(Dev& dv, Job j, hipStream_t st, bool count, uint32_t* ct_blocks = nullptr, const hipStream_t* sched_st = nullptr,
+           bool* presented = nullptr)
+{
+    LaunchSched ls;
+    int rc;
+    uint32_t blocks = 0;
+    if ((rc = use_dev(dv)) || (rc = use_sched(dv, sched_key(j), st, &ls, sched_st)) ||
+        (rc = use_ct_slots(dv, ls, st, &j.ct_slots, &j.ct_waves)) ||
+        (rc = launch_with(dv, j, ls, st, count, false, presented, &blocks)))
+        return rc;
+    if (ct_blocks) *ct_blocks = blocks;
+    return queue_done(dv, ls.slot, st, j.ncols > 0 && j.nrows > 0 && j.nframes > 0);   // (the entry point's early return)
 }
 
 // Chained launches (pt_render_device_chain).  A progressive renderer launches the same geometry again
@@ -998,90 +946,38 @@ int chain_setup(Dev& dv, Sched& sc)
     return PT_OK;
 }
 
-int v4_launch(Dev& dv, PtV4Job j, hipStream_t st, bool count, bool* presented = nullptr, uint32_t* ct_blocks = nullptr,
-              const hipStream_t* sched_st = nullptr);
-
-// What differs between the diffuse and the v4 renderer in launch_chain: the schedule's key, whether
-// the launch variant is settled (the diffuse kernels time their arms on a geometry's first launches;
-// v4 has one variant), the restarting launch (launch / v4_launch) and the continuing one.
-SchedKey chain_key(const PtJob& j)
-{
-    SchedKey k = sched_key(j);
-    k.split = j.nframes <= 8 ? g.split : 0u;   // (as launch())
-    return k;
-}
-SchedKey chain_key(const PtV4Job& j) { return sched_key(j); }   // (v4 takes whole tiles: v4_launch)
+// Whether the launch variant no longer depends on timing (the diffuse kernels time their arms on a
+// geometry's first launches; v4 has one variant).
 bool chain_variant_fixed(const PtJob& j, const Sched& sc)
 {
-    const bool env_arms = j.env && j.nframes <= 16 && g.ct_back_pct != 0 && !g.back_set;   // (ct_occupancy)
-    return g.ct_waves || g.ct_seq_len || sc.wide >= 0 || (j.env && !env_arms);
+    const bool env = j.env != nullptr;   // (without arms: ct_occupancy leaves it the fixed variant)
+    return g.ct_waves || g.ct_seq_len || sc.wide >= 0 ||
+           (env && !pt_plan_env_arms(env, pt_plan_back(j.nframes, g.ct_back_pct), g.back_set));
 }
 bool chain_variant_fixed(const PtV4Job&, const Sched&) { return true; }
-int chain_restart(Dev& dv, const PtJob& j, hipStream_t X, uint32_t* blocks, const hipStream_t* s)
-{
-    return launch(dv, j, X, false, blocks, s);
-}
-int chain_restart(Dev& dv, const PtV4Job& j, hipStream_t X, uint32_t* blocks, const hipStream_t* s)
-{
-    return v4_launch(dv, j, X, false, nullptr, blocks, s);
-}
-// A continuing chained launch that takes back claims (<= 16 frames) takes ALL its dynamic units from
-// the back (cheapest first, after each wave's static first unit): its tail overlaps the next launch,
-// so the launch-end balancing of the timed share no longer pays, and the reversed order measured faster
-// (3 interleaved rounds, profiles/r06/r06u_*: c2 0.2180 vs 0.2207 ms at the timed 45 %, v4 0.3302 vs
-// 0.3468 at its 20 %; the env kernel showed no difference, r06v: it keeps its timed share).  Launches of
-// more frames keep claiming from the front (4K 64 spp 5.55 vs 5.62 ms with back claims, r06x).
-constexpr uint32_t kChainBack = 100;
-int chain_continue(Dev& dv, PtJob& j, Sched* sc, hipStream_t X, uint32_t* blocks)
-{
-    int rc;
-    j.scene = dv.dscene;
-    j.ct_back_pct = j.nframes <= 16 ? g.ct_back_pct : 0u;   // (as launch())
-    LaunchSched ls;
-    ls.sched = sc;
-    hipEvent_t* tev = nullptr;   // (none: the variant is settled)
-    if ((rc = ct_occupancy(ls, j, &tev, false))) return rc;
-    if (j.ct_back_pct != 0 && !j.env && !g.back_set) j.ct_back_pct = kChainBack;
-    const bool cam_use = sc->cam && cam_launch_qualifies(*sc, j.nframes);   // (settled: launch_chain continues only then)
-    j.cam_cache = cam_use ? sc->cam : nullptr;
-    j.cam_mode = cam_use ? PT_CAM_USE : PT_CAM_NONE;
-    hipError_t e = pt_launch_render(j, X, false, blocks);
-    if (e != hipSuccess) return fail(PT_EHIP, "render launch failed: %s", hipGetErrorString(e));
-    return PT_OK;
-}
-int chain_continue(Dev& dv, PtV4Job& j, Sched*, hipStream_t X, uint32_t* blocks)
-{
-    if (j.env_mode != PT_V4_ENV_NONE) j.env = dv.denv;   // (as v4_launch())
-    j.ct_force = g.v4_ct_force;
-    j.ct_back_pct = j.nframes <= 16 ? (g.back_set ? g.ct_back_pct : kChainBack) : 0u;   // (kChainBack: above)
-    hipError_t e = pt_launch_v4(j, g.v4scene, X, false, nullptr, blocks);
-    if (e != hipSuccess) return fail(PT_EHIP, "v4 render launch failed: %s", hipGetErrorString(e));
-    return PT_OK;
-}
 
 template <typename Job>
 int launch_chain(Dev& dv, Job j, hipStream_t s)
 {
     int rc;
     if ((rc = use_dev(dv))) return rc;
-    if (dv.chain.off) return chain_restart(dv, j, s, nullptr, nullptr);   // (a plain launch: use_sched joins the chain)
-    const SchedKey key = chain_key(j);
-    // (the continuous-tiles pool and a scheduled geometry: the tile epochs live in its schedule)
-    Sched* sc = g.no_ct || j.ncols <= 0 || j.nrows <= 0 || j.nframes <= 0 ? nullptr : find_sched(dv, key, s);
-    if (!sc) return chain_restart(dv, j, s, nullptr, nullptr);   // (a plain launch: use_sched joins the chain)
-    ct_area_alloc(dv);
-    if ((rc = chain_setup(dv, *sc))) return rc;
     Dev::Chain& c = dv.chain;
-    if (!dv.dct || !c.area1) return chain_restart(dv, j, s, nullptr, nullptr);
-    // what the plain launch's use_sched would do for this launch: build the schedule (restart), record
-    // the costs it is built from (a launch that records them may continue: the overlapped launches
-    // before it do not write them, and the next launch, which builds from them, restarts)
-    const bool builds = sc->have_cost && (!sc->built || sc->launches % g.sched_rebuild == 0);
-    const bool records = !sc->built || (sc->launches + 1) % g.sched_rebuild == 0;
+    // (the continuous-tiles pool and a scheduled geometry: the tile epochs live in its schedule)
+    Sched* sc = c.off || g.no_ct || j.ncols <= 0 || j.nrows <= 0 || j.nframes <= 0 ? nullptr : find_sched(dv, sched_key(j), s);
+    if (sc) {
+        ct_area_alloc(dv);
+        if ((rc = chain_setup(dv, *sc))) return rc;
+    }
+    if (!sc || !dv.dct || !c.area1) return launch(dv, j, s, false);   // (a plain launch: use_sched joins the chain)
+    // what the plain launch's use_sched does for this launch: build the schedule (restart), record the
+    // costs it is built from (a launch that records them may continue: the overlapped launches before
+    // it do not write them, and the next launch, which builds from them, restarts)
+    const PtSchedStep step = pt_plan_sched_step(sc->have_cost, sc->built, sc->launches, g.sched_rebuild);
     // (the camera-hit cache: the launch that fills it and the one after it restart -- no launch reads
     // records while another may still be writing them)
-    const bool cont = c.sched == sc && sc->built && !builds && chain_variant_fixed(j, *sc) &&
-                      cam_chain_may_continue(*sc, j.nframes);
+    const bool cont = pt_plan_chain_continues(
+        c.sched == sc, sc->built, step.builds, chain_variant_fixed(j, *sc),
+        pt_cam_chain_may_continue(cam_launch_qualifies(*sc, j.nframes), sc->cam != nullptr, sc->cam_state));
     const uint32_t seq = sc->chain_seq + 1;
     const int par = cont ? c.par ^ 1 : 0;
     hipStream_t X = c.st[par];
@@ -1097,25 +993,27 @@ int launch_chain(Dev& dv, Job j, hipStream_t s)
         if ((rc = chain_join(dv, X))) return rc;
         HIP_TRY(hipMemsetAsync(c.qblk, 0, 4 * PT_QUEUE_WORDS * sizeof(unsigned), X));
         j.chain_wait = 0;
-        if ((rc = chain_restart(dv, j, X, &blocks, &s))) return rc;   // (slot area dct)
+        if ((rc = launch(dv, j, X, false, &blocks, &s))) return rc;   // (slot area dct)
         c.area = 0;
     } else {
         // continue: once every block of the previous launch has started
         HIP_TRY(hipStreamWaitValue64(X, c.started, c.cum, hipStreamWaitValueGte, ~0ull));
         j.chain_wait = seq - 1;
-        j.queue = c.qblk + (size_t)(seq % 4u) * PT_QUEUE_WORDS;
-        j.queue_next = c.qblk + (size_t)((seq + 2u) % 4u) * PT_QUEUE_WORDS;   // (the launch after next: this stream's)
-        j.order = sc->order;
-        j.units = sc->units;
-        j.nunits = sc->units + 2 * sc->key.ntiles + 1;
-        j.cost = records ? sc->cost : nullptr;
-        if (records) sc->have_cost = true;
-        j.err = dv.derr;
-        c.area ^= 1;
-        j.ct_slots = c.area ? c.area1 : dv.dct;
+        LaunchSched ls;
+        ls.geo = sc;
+        ls.use(*sc);
+        ls.queue = c.qblk + (size_t)(seq % 4u) * PT_QUEUE_WORDS;
+        ls.queue_next = c.qblk + (size_t)((seq + 2u) % 4u) * PT_QUEUE_WORDS;   // (the launch after next: this stream's)
+        ls.cost = step.records ? sc->cost : nullptr;
+        const int area = c.area ^ 1;
+        j.ct_slots = area ? c.area1 : dv.dct;
         j.ct_waves = dv.dct_waves;
+        if ((rc = launch_with(dv, j, ls, X, false, true, nullptr, &blocks))) return rc;
+        // (committed once the kernel is enqueued: a failed launch leaves the chain as its predecessor
+        // left it, and the next one does not take the slot area of a launch that may still be running)
+        c.area = area;
+        if (step.records) sc->have_cost = true;
         ++sc->launches;
-        if ((rc = chain_continue(dv, j, sc, X, &blocks))) return rc;
     }
     c.cum += blocks;
     sc->chain_seq = seq;
@@ -1567,31 +1465,6 @@ int v4_use_env(PtV4Job& j)
     j.env_w = g.env_w;
     j.env_h = g.env_h;
     return PT_OK;
-}
-
-// *ct_blocks, sched_st: as launch()
-int v4_launch(Dev& dv, PtV4Job j, hipStream_t st, bool count, bool* presented, uint32_t* ct_blocks, const hipStream_t* sched_st)
-{
-    LaunchSched ls;
-    int rc;
-    // v4 takes whole tiles: its per-tile kernel runs launches of < 8 frames (and PT_MI355_NO_CT=1), and
-    // split tiles measured slower on the continuous-tiles one (0.3666 vs 0.3633 ms at 1080p 8 spp)
-    if ((rc = use_dev(dv)) || (rc = use_sched(dv, sched_key(j), st, &ls, 0u, sched_st))) return rc;
-    if (j.env_mode != PT_V4_ENV_NONE) j.env = dv.denv;
-    j.queue = ls.queue;
-    j.queue_next = ls.queue_next;
-    j.order = ls.order;
-    j.units = ls.units;
-    j.nunits = ls.nunits;
-    j.cost = ls.cost;
-    j.err = dv.derr;
-    // (the v4 pool's slots per wave: pt_v4_ct_wave_floats() <= pt_ct_wave_floats(), pt_v4.hip)
-    if ((rc = use_ct_slots(dv, ls, st, &j.ct_slots, &j.ct_waves))) return rc;
-    j.ct_force = g.v4_ct_force;
-    j.ct_back_pct = j.nframes <= 16 ? g.ct_back_pct : 0u;   // (as launch())
-    hipError_t e = pt_launch_v4(j, g.v4scene, st, count, presented, ct_blocks);
-    if (e != hipSuccess) return fail(PT_EHIP, "v4 render launch failed: %s", hipGetErrorString(e));
-    return queue_done(dv, ls.slot, st, j.ncols > 0 && j.nrows > 0 && j.nframes > 0);   // (pt_launch_v4's early return)
 }
 
 // The logical device a device-resident job runs on: the device holding its buffer.
@@ -2185,29 +2058,20 @@ int pt_launch_variant(const pt_device_job* dj, int32_t* waves, int32_t* back_pct
     if ((rc = ensure_init()) || (rc = device_job(dj, &j)) || (rc = dev_of(dj->buf, &dv))) return rc;
     if (dj->use_env) j.env = dv->denv;
     if (g.no_ct) return PT_OK;   // (the per-tile pools)
-    const bool back = j.nframes <= 16;
-    const uint32_t dflt = back ? g.ct_back_pct : 0u;
-    if (g.ct_waves) {   // fixed (launch(), ct_occupancy)
-        *waves = j.env ? pt_ct_env_waves() : (int32_t)g.ct_waves;
-        *back_pct = (int32_t)dflt;
-        return PT_OK;
-    }
-    SchedKey key = sched_key(j);
-    key.split = j.nframes <= 8 ? g.split : 0u;
-    if (key.ntiles < kSchedMinTiles) {   // never scheduled, never timed: the fixed fallback (ct_occupancy)
-        *waves = j.env ? pt_ct_env_waves() : 5;
+    const bool env = j.env != nullptr;
+    const uint32_t dflt = pt_plan_back(j.nframes, g.ct_back_pct);
+    const SchedKey key = sched_key(j);
+    // fixed (ct_occupancy): by the switch, or a geometry that is never scheduled, so never timed
+    if (g.ct_waves || key.ntiles < kSchedMinTiles) {
+        *waves = env ? pt_ct_env_waves() : g.ct_waves ? (int32_t)g.ct_waves : 5;
         *back_pct = (int32_t)dflt;
         return PT_OK;
     }
     for (const Sched& s : dv->sched) {
         if (!s.used || !(s.key == key) || s.wide < 0) continue;
-        if (j.env) {
-            *waves = pt_ct_env_waves();
-            *back_pct = (int32_t)(s.wide && back && !g.back_set ? kEnvBack[s.wide] : dflt);
-        } else {
-            *waves = s.wide ? 6 : 5;
-            *back_pct = (int32_t)(s.wide == 2 && back ? kBackWide : dflt);
-        }
+        const PtVariant v = pt_plan_variant(env, s.wide, dflt, g.back_set);   // (the pick, as ct_occupancy applies it)
+        *waves = env ? pt_ct_env_waves() : v.wide ? 6 : 5;
+        *back_pct = (int32_t)v.back_pct;
         return PT_OK;
     }
     return PT_OK;   // (undecided)
@@ -2260,8 +2124,7 @@ int pt_cam_cache_query(const pt_device_job* dj, void* stream, int32_t* state, ui
     if ((rc = ensure_init()) || (rc = device_job(dj, &j)) || (rc = dev_of(dj->buf, &dv))) return rc;
     if (dj->use_env) j.env = dv->denv;
     *compared = dv->cam_checked;
-    SchedKey key = sched_key(j);
-    key.split = j.nframes <= 8 ? g.split : 0u;   // (as launch())
+    const SchedKey key = sched_key(j);
     for (const Sched& s : dv->sched) {
         if (!s.used || s.stream != (hipStream_t)stream || !(s.key == key)) continue;
         if (s.cam && cam_launch_qualifies(s, j.nframes))
@@ -2448,7 +2311,7 @@ int pt_render_opt_v4(float* buf, int32_t w, int32_t h, int32_t ntx, int32_t nty,
     j.tile_h = th;
     if ((rc = v4_use_env(j))) return rc;
     bool banded = false;   // PT_FLAG_PIN_HOST: bands of whole tile rows
-    if ((rc = render_bands(buf, j, th, [](const PtV4Job& b) { return v4_launch(g.dev[0], b, g.dev[0].stream, false); },
+    if ((rc = render_bands(buf, j, th, [](const PtV4Job& b) { return launch(g.dev[0], b, g.dev[0].stream, false); },
                            &banded)))
         return rc;
     const Geo geo = geo_of(w, h, PT_LAYOUT_TILED_PLANAR8, tw, th);
@@ -2466,7 +2329,7 @@ int pt_render_opt_v4(float* buf, int32_t w, int32_t h, int32_t ntx, int32_t nty,
                 jd.pix_xrgb = 1;
                 jd.pix_fast_tone = g.v4cfg.fast_aces && g.v4cfg.fast_gamma ? 1 : 0;
             }
-            if ((rc = v4_launch(g.dev[d], jd, g.dev[d].stream, false, &presented))) return rc;
+            if ((rc = launch(g.dev[d], jd, g.dev[d].stream, false, nullptr, nullptr, &presented))) return rc;
         }
     }
     g.v4_frame += 1;   // iFrame += 1.0f (v4 :1703), before rendering
@@ -2535,7 +2398,7 @@ int pt_v4_render_device(const pt_device_job* dj, void* stream)
     Dev* dv = nullptr;
     DeviceGuard guard;
     if ((rc = ensure_init()) || (rc = v4_device_job(dj, &j)) || (rc = dev_of(dj->buf, &dv))) return rc;
-    return v4_launch(*dv, j, (hipStream_t)stream, false);
+    return launch(*dv, j, (hipStream_t)stream, false);
 }
 
 // pt_render_device_present for v4: the continuous-tiles kernel's presenting instances write the pixels
@@ -2556,7 +2419,7 @@ int pt_v4_render_device_present(const pt_device_job* dj, uint32_t* pixels, int32
     j.pix_xrgb = format == PT_PIXEL_XRGB8;
     j.pix_fast_tone = g.v4cfg.fast_aces && g.v4cfg.fast_gamma ? 1 : 0;
     bool presented = false;
-    if ((rc = v4_launch(*dv, j, (hipStream_t)stream, false, &presented)) || presented) return rc;
+    if ((rc = launch(*dv, j, (hipStream_t)stream, false, nullptr, nullptr, &presented)) || presented) return rc;
     const PtToneJob tj = tone_job(j.buf, j.ncols, j.nrows, j.layout, 0, 0, pixels, format);   // (the v4 config's flags)
     hipError_t e = pt_launch_tonemap(tj, (hipStream_t)stream);
     if (e != hipSuccess) return fail(PT_EHIP, "tonemap launch failed: %s", hipGetErrorString(e));
@@ -2584,7 +2447,7 @@ int pt_v4_count_device(const pt_device_job* dj, void* stream, pt_work_counts* ou
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(dv->dcounters, 0, kCounterSlots * sizeof(unsigned long long), st));
     j.counters = dv->dcounters;
-    if ((rc = v4_launch(*dv, j, st, true))) return rc;
+    if ((rc = launch(*dv, j, st, true))) return rc;
     unsigned long long h[6];
     HIP_TRY(hipMemcpyAsync(h, dv->dcounters, sizeof(h), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -2689,7 +2552,7 @@ int run_queue(pt_work_queue* q, bool wait)
                 j.tile_h = th;
                 j.frame_first = g.v4_frame;
                 if ((rc = v4_use_env(j))) return rc;
-                rc = render_bands(b.data, j, th, [](const PtV4Job& bj) { return v4_launch(g.dev[0], bj, g.dev[0].stream, false); },
+                rc = render_bands(b.data, j, th, [](const PtV4Job& bj) { return launch(g.dev[0], bj, g.dev[0].stream, false); },
                                   &banded);
             } else {
                 pt_tile_info t = t0;
@@ -2744,7 +2607,7 @@ int run_queue(pt_work_queue* q, bool wait)
                     j.row_start = row0;
                     j.nrows = nrows;
                     j.frame_first = g.v4_frame;   // the frame pt_v4_begin_frame started
-                    if ((rc = v4_use_env(j)) || (rc = v4_launch(dv, tile_shard_job(j, d), dv.stream, false))) return rc;
+                    if ((rc = v4_use_env(j)) || (rc = launch(dv, tile_shard_job(j, d), dv.stream, false))) return rc;
                 } else {
                     pt_tile_info t{};
                     t.tile_width = tw;

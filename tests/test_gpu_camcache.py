@@ -7,7 +7,7 @@ instead of tracing; shorter launches trace as ever.  The accumulator must stay t
 (demofox_path_tracing_scalar.cpp:785-820) whichever launch computed a pixel's camera hit, so every
 case here runs launch sequences that fill and then use the cache and compares with
 oracle/pt_oracle.c -- and with the same sequence under PT_MI355_CAM_CACHE=0.  The geometries are the
-smallest that get a schedule entry (>= 512 tiles, pt_capi.cpp kSchedMinTiles) with a width and height
+smallest that get a schedule entry (>= 512 tiles, pt_launch_plan.h kSchedMinTiles) with a width and height
 that are no multiples of 8, so edge tiles have invalid lanes.
 
 Which path the launches took is asserted through pt_cam_cache_query: the cache's state after each

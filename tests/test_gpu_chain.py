@@ -93,7 +93,7 @@ def test_c2_chained_regime_matches_oracle(fresh):
 
 def test_c2_chained_whole_image_matches_oracle(fresh):
     """configs[1] chained at 6 waves per SIMD (the timing's pick for it), 24 launches -- all but the
-    first two continue the overlap, claiming their dynamic units cheapest-first (pt_capi.cpp
+    first two continue the overlap, claiming their dynamic units cheapest-first (pt_launch_plan.h
     kChainBack): the whole image after 192 frames equals the oracle bit for bit (a stale accumulator
     read would show as scattered pixels)."""
     W, H, B, S = 1920, 1080, 8, 8
