@@ -52,6 +52,9 @@ from .renderer import (  # noqa: F401
     unpin_host,
     release_buffer,
     v4_get_config,
+    v4_camera,
+    v4_get_camera,
+    v4_sky_window,
     WriteImage,
 )
 
@@ -63,5 +66,5 @@ __all__ = [
     "ClearScene", "AddMaterialToScene", "AddQuadObjectToScene", "AddSphereObjectToScene", "LoadCubemapTexture",
     "v4_config", "v4_begin_frame", "v4_get_frame", "v4_set_frame", "MakeWorkQueue", "AddWorkQueueEntry",
     "CompleteAllWork", "WorkQueue", "initialized_device", "initialized_devices", "unpin_host", "release_buffer",
-    "v4_get_config",
+    "v4_get_config", "v4_camera", "v4_get_camera", "v4_sky_window",
 ]

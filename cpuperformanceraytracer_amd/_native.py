@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "pt_v4_add_quad", "pt_v4_add_sphere", "pt_v4_set_frame", "pt_v4_get_frame", "pt_v4_get_scene_tables", "pt_render_opt_v4",
     "pt_copy_output_to_file", "pt_v4_render_device", "pt_v4_render_device_chain", "pt_v4_render_device_present",
     "pt_v4_count_device", "pt_v4_begin_frame",
+    "pt_v4_default_camera", "pt_v4_set_camera", "pt_v4_get_camera", "pt_v4_get_sky_window",
     "pt_make_work_queue", "pt_add_work_queue_entry", "pt_complete_all_work", "pt_complete_all_work_async",
     "pt_wait_work", "pt_work_queue_size", "pt_free_work_queue",
 )
@@ -111,6 +112,10 @@ class PtV4Material(ctypes.Structure):
                 ("specular_color", ctypes.c_float * 3), ("ior", ctypes.c_float),
                 ("refraction_chance", ctypes.c_float), ("refraction_roughness", ctypes.c_float),
                 ("refraction_color", ctypes.c_float * 3)]
+
+
+class PtV4Camera(ctypes.Structure):
+    _fields_ = [("position", ctypes.c_float * 3), ("fov_degrees", ctypes.c_float)]
 
 
 class PtError(RuntimeError):
@@ -200,6 +205,10 @@ def load() -> ctypes.CDLL:
         "pt_v4_render_device_present": (i32, [ctypes.POINTER(PtDeviceJob), vp, i32, vp]),
         "pt_v4_count_device": (i32, [ctypes.POINTER(PtDeviceJob), vp, ctypes.POINTER(PtWorkCounts)]),
         "pt_v4_begin_frame": (i32, []),
+        "pt_v4_default_camera": (None, [ctypes.POINTER(PtV4Camera)]),
+        "pt_v4_set_camera": (i32, [ctypes.POINTER(PtV4Camera)]),
+        "pt_v4_get_camera": (i32, [ctypes.POINTER(PtV4Camera), ctypes.POINTER(ctypes.c_float)]),
+        "pt_v4_get_sky_window": (i32, [vp, i32, ctypes.POINTER(i32)]),
         "pt_make_work_queue": (vp, [i32]),
         "pt_add_work_queue_entry": (i32, [vp, ctypes.POINTER(PtBufferInfo), ctypes.POINTER(PtTileInfo)]),
         "pt_complete_all_work": (i32, [vp]),

@@ -23,6 +23,7 @@
 #include "pt_output.h"
 #include "pt_v4.h"
 #include "../../include/pt_mi355.h"
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -191,6 +192,13 @@ struct State {
     PtV4SceneDesc v4desc{};
     PtV4Scene v4scene{};
     uint32_t v4_frame = 0;
+    // the v4 camera (pt_v4_set_camera): InitializeCamera's position and field of view (v4 :1500-1501,
+    // :20), the distance computed from it, and the sky window of (v4desc, camera) -- rebuilt by the
+    // first job after either changed
+    pt_v4_camera v4cam{{0.0f, 0.0f, 40.0f}, 90.0f};
+    float v4cam_dist = 1.0f;
+    PtV4SkyWin v4sky{-1, {}};
+    bool v4sky_ready = false;
     // test hook: PT_MI355_RING_GUARD_CAP (read by pt_init) caps the pools' iteration guards so
     // that it fires -- the error path's own GPU test (tests/test_gpu_state.py)
     uint32_t ring_guard_cap = ~0u;
@@ -1423,7 +1431,29 @@ int v4_rebuild()
         return fail(PT_EINVAL, "v4 scene exceeds MAX_OBJECTS (%d quads + %d spheres, %d materials; limit %d)",
                     g.v4desc.nquads, g.v4desc.nspheres, g.v4desc.nmat, PT_V4_MAX_OBJECTS);
     g.v4_scene_ready = true;
+    g.v4sky_ready = false;
     return PT_OK;
+}
+
+// The sky window of the current (scene, camera) (pt_v4_skywin.h): host arithmetic, built on first use
+// after a scene edit or a camera change.  PT_MI355_V4_SKYWIN=0: no window (A/B timing, tests).
+const PtV4SkyWin& v4_sky_window()
+{
+    if (!g.v4sky_ready) {
+        static const bool off = getenv("PT_MI355_V4_SKYWIN") && !strcmp(getenv("PT_MI355_V4_SKYWIN"), "0");
+        if (off) g.v4sky = PtV4SkyWin{-1, {}};
+        else pt_v4_skywin_build(g.v4desc.nquads, g.v4desc.quad, g.v4desc.nspheres, g.v4desc.sphere, g.v4cam.position, &g.v4sky);
+        g.v4sky_ready = true;
+    }
+    return g.v4sky;
+}
+
+// camera.Distance of InitializeCamera (v4 :1500): 1.0f / tanf(c_FOVDegrees * 0.5f * c_pi / 180.0f) in
+// f32, c_pi = 3.14159265359f (mathutils.h:5); glibc tanf for MSVC's float overload
+float v4_camera_distance(float fov_degrees)
+{
+    const float c_pi = 3.14159265359f;
+    return 1.0f / tanf(fov_degrees * 0.5f * c_pi / 180.0f);
 }
 
 int v4_ensure_scene()
@@ -1453,7 +1483,13 @@ PtV4Job v4_job(float* buf, int32_t w, int32_t h)
     j.rejection = g.v4cfg.rejection;
     j.accumulate = g.v4cfg.accumulate_frames;   // ACCUMULATE_FRAMES (flags.h:60)
     j.fast_exp = g.v4cfg.fast_exp;              // USE_FAST_APPROXIMATE_EXP (flags.h:64)
-    j.default_scene = pt_v4_is_default_geometry(g.v4scene) ? 1 : 0;
+    memcpy(j.cam_pos, g.v4cam.position, sizeof(j.cam_pos));
+    j.cam_dist = g.v4cam_dist;
+    // the literal-geometry instances also carry the default camera as literals: InitializeScene seen by
+    // a camera bit-equal to (0, 0, 40), distance 1.0f; every other camera runs the generic instances
+    const float cam_default[4] = {0.0f, 0.0f, 40.0f, 1.0f}, cam[4] = {j.cam_pos[0], j.cam_pos[1], j.cam_pos[2], j.cam_dist};
+    j.default_scene = pt_v4_is_default_geometry(g.v4scene) && !memcmp(cam, cam_default, sizeof(cam)) ? 1 : 0;
+    j.sky = v4_sky_window();   // (read by the generic instances only)
     return j;
 }
 
@@ -2288,6 +2324,59 @@ int pt_v4_get_scene_tables(float* out, int32_t n, int32_t* nq, int32_t* ns)
         o += 4;
     }
     memcpy(o, s.mat, sizeof(s.mat));
+    return need;
+}
+
+void pt_v4_default_camera(pt_v4_camera* c)
+{
+    if (!c) return;
+    c->position[0] = 0.0f;   // camera.Position = float3(0, 0, c_cameraDistance * 40), v4 :1501
+    c->position[1] = 0.0f;
+    c->position[2] = 1.0f * 40.0f;
+    c->fov_degrees = 90.0f;  // c_FOVDegrees, v4 :20
+}
+
+int pt_v4_set_camera(const pt_v4_camera* c)
+{
+    if (!c) return fail(PT_EINVAL, "null v4 camera");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(c->position[k]) || std::fabs(c->position[k]) > 1024.0f)
+            return fail(PT_EINVAL, "camera position[%d] = %g is not finite or beyond +-1024", k, (double)c->position[k]);
+    if (!std::isfinite(c->fov_degrees) || !(c->fov_degrees > 0.0f && c->fov_degrees < 180.0f))
+        return fail(PT_EINVAL, "fov_degrees %g outside (0, 180)", (double)c->fov_degrees);
+    const float dist = v4_camera_distance(c->fov_degrees);
+    if (!(std::isnormal(dist) && dist > 0.0f))
+        return fail(PT_EINVAL, "fov_degrees %g gives the camera distance %g, not a finite positive normal f32",
+                    (double)c->fov_degrees, (double)dist);
+    g.v4cam = *c;
+    g.v4cam_dist = dist;
+    g.v4sky_ready = false;
+    // a live v4 chain ends: the next chained launch restarts, as after any other non-chained launch.
+    // (The tile schedules are kept: the order only affects speed, and the periodic rebuild picks the new
+    // view's costs up, as after a scene edit -- DESIGN.md 3b.)
+    for (int d = 0; d < g.ndev; ++d)
+        if (g.dev[d].chain.sched && g.dev[d].chain.sched->key.kind >= 1) g.dev[d].chain.sched = nullptr;
+    return PT_OK;
+}
+
+int pt_v4_get_camera(pt_v4_camera* c, float* distance)
+{
+    if (!c) return fail(PT_EINVAL, "null v4 camera");
+    *c = g.v4cam;
+    if (distance) *distance = g.v4cam_dist;
+    return PT_OK;
+}
+
+int pt_v4_get_sky_window(float* rects, int32_t n, int32_t* nrects)
+{
+    int rc;
+    if (!nrects) return fail(PT_EINVAL, "null nrects");
+    if ((rc = v4_ensure_scene())) return rc;
+    const PtV4SkyWin& w = v4_sky_window();
+    *nrects = w.nrects;
+    const int32_t need = w.nrects > 0 ? 4 * w.nrects : 0;
+    if (!rects || n < need) return need;
+    memcpy(rects, w.rect, (size_t)need * sizeof(float));
     return need;
 }
 

@@ -4,7 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pt_v4_skywin.h"
+
 #define PT_V4_MAX_OBJECTS 12   // MAX_OBJECTS / MAX_MATERIALS, v4 :351-352
+static_assert(PT_V4_SKYWIN_MAX == PT_V4_MAX_OBJECTS, "one sky-window rectangle per object");
 
 // env modes (global_preprocessor_flags.h:58-59)
 #define PT_V4_ENV_NONE_ 0       // USE_ENV_MAP 0: ambient (0.11, 0.1, 0.15), v4 :782
@@ -89,7 +92,15 @@ struct PtV4Job {
     // kernel's presenting instances); 0 = the full image, as above.  (Last: in the struct's tail
     // padding, so no other member's kernel-argument offset moved when it was added.)
     int32_t pix_rows;
+    // the camera (camera.Position, camera.Distance: v4 :1500-1501, read by mainImage :1112, :1128) and
+    // the sky window of (scene, camera) (pt_v4_skywin.h; nrects -1: none).  Appended: no member above
+    // moved.  Read by the generic instances only -- default_scene is set only with the default camera,
+    // bit-equal to (0, 0, 40) and 1.0f, which the DEF instances carry as literals (with sky_ray_v4).
+    float cam_pos[3];
+    float cam_dist;
+    PtV4SkyWin sky;
 };
+static_assert(sizeof(PtV4Job) + sizeof(PtV4Scene) <= 4096, "kernel arguments (job, scene) exceed the 4 KiB limit");
 
 // Scene description in AddQuad/Sphere/MaterialToScene order (v4 :1368-1401).
 struct PtV4SceneDesc {

@@ -40,6 +40,7 @@
 #include "pt_wave.h"
 #include "pt_tonemap.h"
 #include <algorithm>
+#include <cstring>
 
 namespace {
 
@@ -483,6 +484,46 @@ __device__ __forceinline__ bool sky_ray_v4(V3 D)
 }
 static_assert(pt_v4_default::kQuads == 4 && pt_v4_default::kSpheres == 7, "sky_ray_v4 is derived for InitializeScene");
 
+// The camera of a launch: camera.Distance and camera.Position (InitializeCamera v4 :1500-1501) as
+// mainImage reads them (:1112, :1128), and the sky test of its camera rays.  DEF (InitializeScene seen
+// by the default camera -- the host sets default_scene only when position and distance are bit-equal to
+// (0, 0, 40) and 1.0f): the literals and sky_ray_v4; the job's camera fields are not read.  Otherwise
+// the job's camera (kernel arguments: wave-uniform, scalar registers) and sky window (pt_v4_skywin.h).
+template <bool DEF>
+struct V4Cam {
+    const PtV4Job& job;
+    __device__ __forceinline__ explicit V4Cam(const PtV4Job& j) : job(j) {}
+    // normalize((tx, ty, -Distance) - (0, 0, 0)), :1112-1113
+    __device__ __forceinline__ V3 ray(float tx, float ty) const
+    {
+        if constexpr (DEF) {
+            // 1 / tanf(c_FOVDegrees * 0.5f * c_pi / 180.0f) == 1.0f exactly; |(tx, ty, -1)| >= 1 and tx,
+            // ty are O(1): no range guards
+            const V3 cv = v3(tx, ty, -1.0f) - v3(0.0f, 0.0f, 0.0f);
+            return cv * pt::rcp_rn(pt::sqrt_rn(dot(cv, cv)));
+        } else {
+            // any finite positive normal distance: the guarded forms (IEEE for every input)
+            return normalize(v3(tx, ty, -job.cam_dist) - v3(0.0f, 0.0f, 0.0f));
+        }
+    }
+    __device__ __forceinline__ V3 position() const
+    {
+        if constexpr (DEF) return v3(0.0f, 0.0f, 1.0f * 40.0f);   // camera.Position :1501
+        else return v3(job.cam_pos[0], job.cam_pos[1], job.cam_pos[2]);
+    }
+    __device__ __forceinline__ bool has_sky() const
+    {
+        if constexpr (DEF) return true;
+        else return job.sky.nrects >= 0;
+    }
+    // a camera ray that certainly misses every primitive
+    __device__ __forceinline__ bool sky(V3 d) const
+    {
+        if constexpr (DEF) return sky_ray_v4(d);
+        else return pt_v4_skywin_sky(job.sky, d.x, d.y, d.z);
+    }
+};
+
 // TestSceneTrace :700-718: quads in order, then spheres (object index = material index).
 // DEF: the reference's InitializeScene, geometry as instruction literals (pt_v4_default_scene.h,
 // generated from pt_v4_build_scene and checked by tests/test_oracle_v4.py); otherwise the scene
@@ -817,7 +858,7 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_OCC void pt_v4_kernel(PtV4Job jo
     const int B = job.num_bounces;
     const float W = (float)job.width, H = (float)job.height;
     const float rW = rcp(W), rH = rcp(H);
-    const float cam_dist = 1.0f;   // 1 / tanf(c_FOVDegrees * 0.5f * c_pi / 180.0f) == 1.0f exactly (InitializeCamera :1500)
+    const V4Cam<DEF> cam(job);   // camera.Distance, camera.Position (InitializeCamera :1500-1501)
     unsigned long long n_seg = 0, n_esc = 0, n_slots = 0, n_fb = 0, n_sky = 0;
 
     // persistent waves: 8x8 tiles from the launch's queue (pt_tile_queue.h), longest first when the
@@ -897,10 +938,8 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_OCC void pt_v4_kernel(PtV4Job jo
                         const float tx = fma_(((float)X + jx) * rW, 2.0f, -1.0f);
                         float ty = fma_(((float)fyi + jy) * rH, 2.0f, -1.0f);
                         ty = ty * (rW * H);
-                        // |(tx, ty, -1)| >= 1 and tx, ty are O(1): no range guards
-                        const V3 cv = v3(tx, ty, -cam_dist) - v3(0.0f, 0.0f, 0.0f);
-                        dir = cv * pt::rcp_rn(pt::sqrt_rn(dot(cv, cv)));
-                        pos = v3(0.0f, 0.0f, 1.0f * 40.0f);   // camera.Position :1501
+                        dir = cam.ray(tx, ty);
+                        pos = cam.position();
                         T = v3(1.0f, 1.0f, 1.0f);
                         ret = v3(0.0f, 0.0f, 0.0f);
                         bounce = 0;
@@ -917,9 +956,10 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_OCC void pt_v4_kernel(PtV4Job jo
             // silhouette (sky_ray_v4), the wave skips TestSceneTrace -- the reference's miss
             // (the slope test runs only in iterations where every busy lane is at bounce 0: a wave-
             // uniform branch, instead of the test on every lane in every iteration)
+            // any other (scene, camera): the same with its sky window (pt_v4_skywin.h), when it has one
             bool all_sky = false;
-            if (DEF && pt_ballot(item >= 0 && bounce != 0) == 0)
-                all_sky = pt_ballot(item >= 0 && !sky_ray_v4(dir)) == 0;
+            if (cam.has_sky() && pt_ballot(item >= 0 && bounce != 0) == 0)
+                all_sky = pt_ballot(item >= 0 && !cam.sky(dir)) == 0;
             if (item >= 0) {
                 bool done = false;
                 v4_segment<ENV, COUNT, DEF, FEXP, DFL>(job, sc, s_mat, s_mx, s_sc, tex, random, rejection, B, all_sky, pos,
@@ -1099,7 +1139,7 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_CT_OCC void pt_v4_ct_kernel(PtV4
     const int B = job.num_bounces;
     const float W = (float)job.width, H = (float)job.height;
     const float rW = rcp(W), rH = rcp(H);
-    const float cam_dist = 1.0f;   // (as pt_v4_kernel, InitializeCamera :1500)
+    const V4Cam<DEF> cam(job);   // (as pt_v4_kernel, InitializeCamera :1500-1501)
     unsigned long long n_seg = 0, n_esc = 0, n_slots = 0, n_fb = 0, n_sky = 0;
     // the fused output stage: pixel column X of job row pr, with its final accumulator value
     auto present = [&](int X, int pr, const V3& acc) {
@@ -1176,8 +1216,7 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_CT_OCC void pt_v4_ct_kernel(PtV4
         const float tx = fma_(((float)X + jx) * rW, 2.0f, -1.0f);
         float ty = fma_(((float)fyi + jy) * rH, 2.0f, -1.0f);
         ty = ty * (rW * H);
-        const V3 cv = v3(tx, ty, -cam_dist) - v3(0.0f, 0.0f, 0.0f);
-        d = cv * pt::rcp_rn(pt::sqrt_rn(dot(cv, cv)));
+        d = cam.ray(tx, ty);
     };
     // Start chunks until A is set or the queue is done: the current tile's next chunk, or a new tile
     // (its valid pixels listed; a new tile starts only when the previous tile's last chunk has handed
@@ -1224,8 +1263,9 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_CT_OCC void pt_v4_ct_kernel(PtV4
             // their trace when every busy lane holds such a ray, which the pool's mix of tiles
             // rarely allows -- half of the 1080p tiles are sky.  Each is the pool's miss at bounce 0
             // (T = 1, ret = 0: v4_segment, resolve) and the fold's lerp, with the same operations.
+            // (any other (scene, camera): the same with its sky window, when it has one)
             int fsky = 0;
-            if (DEF) {
+            if (cam.has_sky()) {
                 const int orow = LAYOUT == PT_LAYOUT_TILED_PLANAR8 ? job.row_start + pr * job.row_stride : pr;
                 size_t pi = valid ? out_index<LAYOUT>(job, X, orow) : 0;
                 if (valid && !PT_GUARD(job.err, pi + 2 * cs < px_extent, PT_G_PIXEL, pi)) pi = 0;   // (checked build: reported)
@@ -1235,7 +1275,7 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_CT_OCC void pt_v4_ct_kernel(PtV4
                     uint32_t r;
                     V3 d;
                     camera(X, fyi, job.frame_first + (uint32_t)fsky, r, d);
-                    if (pt_ballot(valid && !sky_ray_v4(d)) != 0) break;
+                    if (pt_ballot(valid && !cam.sky(d)) != 0) break;
                     if (COUNT) n_slots += 64;
                     if (valid) {
                         V3 amb = v3(0.11f, 0.1f, 0.15f);   // :782
@@ -1380,7 +1420,7 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_CT_OCC void pt_v4_ct_kernel(PtV4
                     const int p = (int)(pl & 63u), X = (int)(pl >> 8);
                     const int fyi = (int)s_py[wv][sl];
                     camera(X, fyi, fA + (uint32_t)fi, rng, dir);
-                    pos = v3(0.0f, 0.0f, 1.0f * 40.0f);   // camera.Position :1501
+                    pos = cam.position();
                     T = v3(1.0f, 1.0f, 1.0f);
                     ret = v3(0.0f, 0.0f, 0.0f);
                     bounce = 0;
@@ -1395,7 +1435,7 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_CT_OCC void pt_v4_ct_kernel(PtV4
             if (COUNT) n_slots += 64;
             const bool busy = had || took;
             bool all_sky = false;   // (as pt_v4_kernel)
-            if (DEF && pt_ballot(busy && bounce != 0) == 0) all_sky = pt_ballot(busy && !sky_ray_v4(dir)) == 0;
+            if (cam.has_sky() && pt_ballot(busy && bounce != 0) == 0) all_sky = pt_ballot(busy && !cam.sky(dir)) == 0;
             bool done = false, queued = false;
             int qslot = 0;
             if (busy) {
@@ -1601,6 +1641,10 @@ hipError_t pt_launch_v4(const PtV4Job& j_in, const PtV4Scene& sc, hipStream_t st
     //    continuous-tiles kernel takes (launch_t decides: *presented), the default scene with the
     //    default sampling flags or a generic scene.
     PtV4Job j = j_in;
+    if (j.sky.nrects > PT_V4_SKYWIN_MAX) return hipErrorInvalidValue;
+    // the DEF instances carry the default camera as literals: any other camera runs the generic ones
+    const float cam_default[4] = {0.0f, 0.0f, 40.0f, 1.0f}, cam[4] = {j.cam_pos[0], j.cam_pos[1], j.cam_pos[2], j.cam_dist};
+    if (memcmp(cam, cam_default, sizeof(cam)) != 0) j.default_scene = 0;
     const bool tiled = j.layout == PT_LAYOUT_TILED_PLANAR8;
     const bool tone = j.fast_exp && j.pix_fast_tone && !count;
     const bool dflt = j.default_scene && j.random_jitter && j.rejection;

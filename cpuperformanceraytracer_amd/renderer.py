@@ -488,6 +488,34 @@ def v4_scene_tables() -> tuple[np.ndarray, int, int]:
     return out, nq.value, ns.value
 
 
+def v4_camera(position=(0.0, 0.0, 40.0), fov_degrees: float = 90.0) -> None:
+    """The v4 camera (camera.Position, c_FOVDegrees: v4 :1501, :20) for every v4 entry point; the view
+    direction stays -z with no roll, as the reference's.  Host state only: the frame counter and the
+    accumulators are untouched (a host that moves the camera restarts its own accumulation)."""
+    c = N.PtV4Camera((ctypes.c_float * 3)(*position), fov_degrees)
+    N.check(N.load().pt_v4_set_camera(ctypes.byref(c)), "pt_v4_set_camera")
+
+
+def v4_get_camera() -> dict:
+    """{position, fov_degrees, distance}: distance is camera.Distance, 1 / tanf(fov / 2) in f32."""
+    c, d = N.PtV4Camera(), ctypes.c_float()
+    N.check(N.load().pt_v4_get_camera(ctypes.byref(c), ctypes.byref(d)), "pt_v4_get_camera")
+    return {"position": tuple(float(v) for v in c.position), "fov_degrees": float(c.fov_degrees), "distance": float(d.value)}
+
+
+def v4_sky_window() -> tuple[int, np.ndarray]:
+    """The sky window of the current (scene, camera) (pt_v4_get_sky_window): (nrects, rects), rects
+    nrects x 4 f32 slope bounds sx_lo, sx_hi, sy_lo, sy_hi per object; nrects -1: no window."""
+    L = N.load()
+    nr = ctypes.c_int32()
+    need = L.pt_v4_get_sky_window(None, 0, ctypes.byref(nr))
+    if need < 0:
+        N.check(need, "pt_v4_get_sky_window")
+    out = np.zeros(need, np.float32)
+    N.check(0 if L.pt_v4_get_sky_window(out.ctypes.data, need, ctypes.byref(nr)) == need else -1, "pt_v4_get_sky_window")
+    return nr.value, out.reshape(-1, 4)
+
+
 def v4_begin_frame() -> None:
     """iFrame += 1 of DemofoxRenderOptV4 (v4 :1703) without rendering (hosts that queue tiles)."""
     N.check(N.load().pt_v4_begin_frame(), "pt_v4_begin_frame")

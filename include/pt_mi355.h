@@ -276,6 +276,34 @@ uint32_t pt_v4_get_frame(void);
  * pt_v4_material order).  Returns the number of floats written (or needed, when n is too small),
  * with *nquads / *nspheres set; PT_E* on error. */
 int pt_v4_get_scene_tables(float* out, int32_t n, int32_t* nquads, int32_t* nspheres);
+/* The camera: the reference's run-time camera object (camera.Position, camera.Distance, read by mainImage
+ * v4 :1112, :1128 and filled by InitializeCamera :1500-1501 from c_FOVDegrees :20).  The distance is
+ * computed on the host in f32 with the reference's expression, 1.0f / tanf(fov_degrees * 0.5f * c_pi /
+ * 180.0f) (90 degrees: exactly 1.0f).  The view direction stays -z with no roll, as in the reference:
+ * its camera has no orientation, and a rotation would be arithmetic with no counterpart in the
+ * reference to be bit-exact against, so there is none here.
+ * pt_v4_set_camera is pure host state like pt_v4_set_config (no GPU, no pt_init; reset with the config
+ * by pt_shutdown) and applies to every v4 entry point on every device: pt_render_opt_v4, v4 work
+ * queues, pt_v4_render_device / _chain / _present and pt_v4_count_device.  It touches neither the v4
+ * frame counter nor any accumulator -- a host that moves the camera restarts its own accumulation,
+ * as a reference host would -- and it ends a live v4 chain (the next pt_v4_render_device_chain call
+ * restarts).  PT_EINVAL: a null pointer, a non-finite field, fov_degrees outside (0, 180), a distance
+ * that is not a finite positive normal f32, |position component| > 1024. */
+typedef struct pt_v4_camera {
+    float position[3];   /* camera.Position (v4 :1501); default (0, 0, 40) */
+    float fov_degrees;   /* c_FOVDegrees (v4 :20); default 90              */
+} pt_v4_camera;
+void pt_v4_default_camera(pt_v4_camera* cam);
+int pt_v4_set_camera(const pt_v4_camera* cam);
+int pt_v4_get_camera(pt_v4_camera* cam, float* distance /* camera.Distance; may be NULL */);
+/* introspection (host only): the sky window of the current (scene, camera) -- per object (quads first)
+ * one rectangle sx_lo, sx_hi, sy_lo, sy_hi (4 f32) of ray slopes D.x / -D.z, D.y / -D.z; a camera ray
+ * outside every rectangle misses the scene, and the kernels skip TestSceneTrace for waves of such
+ * rays.  *nrects = the number of rectangles, or -1: no window (an object less than 1.0 in front of the
+ * camera, or a coordinate that is not finite or beyond +-1024), nothing is skipped.  `rects` holds n
+ * f32; returns the number of floats written (or needed, when rects is NULL or n is too small), PT_E* on
+ * error. */
+int pt_v4_get_sky_window(float* rects, int32_t n, int32_t* nrects);
 /* replaces DemofoxRenderOptV4 (v4 .h:14, .cpp:1696-1721): advance iFrame, render every tile into the
  * tiled accumulator (RenderTile v4 :1179-1258 layout), then (output_to_screen, screen != NULL) write
  * width*height XRGB8 pixels into `screen`.  tex may be NULL with PT_V4_ENV_NONE. */
