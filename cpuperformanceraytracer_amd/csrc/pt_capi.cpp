@@ -19,6 +19,7 @@
 // the host buffer); transfers move only the owned rows (pitched 2D copies).
 #include "pt_kernel.h"
 #include "pt_guard.h"
+#include "pt_kernel_pick.h"
 #include "pt_launch_plan.h"
 #include "pt_output.h"
 #include "pt_v4.h"
@@ -1485,10 +1486,8 @@ PtV4Job v4_job(float* buf, int32_t w, int32_t h)
     j.fast_exp = g.v4cfg.fast_exp;              // USE_FAST_APPROXIMATE_EXP (flags.h:64)
     memcpy(j.cam_pos, g.v4cam.position, sizeof(j.cam_pos));
     j.cam_dist = g.v4cam_dist;
-    // the literal-geometry instances also carry the default camera as literals: InitializeScene seen by
-    // a camera bit-equal to (0, 0, 40), distance 1.0f; every other camera runs the generic instances
-    const float cam_default[4] = {0.0f, 0.0f, 40.0f, 1.0f}, cam[4] = {j.cam_pos[0], j.cam_pos[1], j.cam_pos[2], j.cam_dist};
-    j.default_scene = pt_v4_is_default_geometry(g.v4scene) && !memcmp(cam, cam_default, sizeof(cam)) ? 1 : 0;
+    // the literal-geometry instances also carry the default camera as literals (pt_v4_camera_is_default)
+    j.default_scene = pt_v4_is_default_geometry(g.v4scene) && pt_v4_camera_is_default(j.cam_pos, j.cam_dist) ? 1 : 0;
     j.sky = v4_sky_window();   // (read by the generic instances only)
     return j;
 }
@@ -2410,7 +2409,7 @@ int pt_render_opt_v4(float* buf, int32_t w, int32_t h, int32_t ntx, int32_t nty,
         for (int d = 0; d < g.ndev; ++d) {
             PtV4Job jd = shard_job(j, d);
             // RenderTile + OutputToScreen in one pass, as the reference's worker does per tile (v4
-            // :1562-1564): one device, the presenting configuration (pt_launch_v4 decides)
+            // :1562-1564): one device, the presenting configuration (pt_pick_v4_normalise decides)
             if (screen && g.v4cfg.output_to_screen && g.ndev == 1) {
                 Dev& dv = g.dev[d];
                 if ((rc = grow(dv, (void**)&dv.dtone_out, &dv.dtone_out_cap, (size_t)w * h * sizeof(uint32_t)))) return rc;
@@ -2491,7 +2490,7 @@ int pt_v4_render_device(const pt_device_job* dj, void* stream)
 }
 
 // pt_render_device_present for v4: the continuous-tiles kernel's presenting instances write the pixels
-// with the accumulator (pt_launch_v4); a launch that did not present -- fewer than 8 frames, the
+// with the accumulator (pt_pick_v4_normalise, pt_pick_v4_ct_takes); a launch that did not present -- fewer than 8 frames, the
 // per-tile pool, sampling flags without a presenting instance, a tonemap pair other than the default
 // fast ACES / gamma, nothing to render -- is followed by the stand-alone pass over the job's rows.
 int pt_v4_render_device_present(const pt_device_job* dj, uint32_t* pixels, int32_t format, void* stream)

@@ -47,6 +47,7 @@
 #define PT_EC_SQRT(x) pt::sqrt_rn(x)                     // t >= 2^-21 where the value is used
 #include "pt_envcert.h"
 #include "pt_tile_queue.h"
+#include "pt_kernel_pick.h"
 #include "pt_guard.h"
 #include "pt_tonemap.h"
 #include "pt_output.h"
@@ -54,6 +55,7 @@
 #include "pt_chain.h"
 #include <math.h>
 #include <algorithm>
+#include <utility>
 
 namespace {
 
@@ -1299,7 +1301,7 @@ __device__ __forceinline__ void render_body_ct(const PtJob& job)
     const int S = job.nframes, B = job.num_bounces;
     const size_t cs = (LAYOUT == PT_LAYOUT_INTERLEAVED) ? 1u : 8u;   // channel stride
     float* const slots = job.ct_slots + (size_t)(blockIdx.x * kWavesPerBlock + wv) * kCtWaveFloats;
-    // (the host launches at most ct_waves waves: launch_ct)
+    // (the host launches at most ct_waves waves: pt_pick_ct_takes)
     if (!PT_GUARD(job.err, blockIdx.x * (uint32_t)kWavesPerBlock + (uint32_t)wv < job.ct_waves, PT_G_SLOT_BASE,
                   blockIdx.x * (uint32_t)kWavesPerBlock + (uint32_t)wv))
         return;
@@ -1842,112 +1844,46 @@ __global__ __launch_bounds__(64 * waves_per_block<true>()) __attribute__((amdgpu
     render_body_ct<LAYOUT, true, COUNT, PRESENT>(job);
 }
 
-template <int LAYOUT, bool ENV, bool COUNT, bool MULTI, bool RING>
-constexpr auto kernel_of()
+// The instance table: entry i is the kernel of kPtKeys[i] (pt_kernel_pick.h).  pt_instance makes an
+// entry's key and its pointer from the same template arguments.
+using PtKernel = void (*)(PtJob);
+struct PtInstance {
+    PtKey key;
+    PtKernel kern;
+};
+template <int LAYOUT, bool ENV, bool COUNT, bool MULTI, bool RING, bool CT, bool WIDE, bool PRESENT>
+constexpr PtInstance pt_instance()
 {
-    if constexpr (ENV) return pt_render_env_kernel<LAYOUT, COUNT, MULTI>;
-    else return pt_render_kernel<LAYOUT, COUNT, MULTI, RING>;
+    // (arguments a kernel does not take are false in its key)
+    static_assert(!(ENV && (RING || WIDE)) && !(CT && (MULTI || RING)) && !(!CT && (WIDE || PRESENT)) && (MULTI || !RING));
+    constexpr PtKey key{LAYOUT, ENV, COUNT, MULTI, RING, CT, WIDE, PRESENT};
+    if constexpr (CT && ENV) return {key, pt_render_ct_env_kernel<LAYOUT, COUNT, PRESENT>};
+    else if constexpr (CT) return {key, pt_render_ct_kernel<LAYOUT, COUNT, WIDE ? 6 : 5, PRESENT>};
+    else if constexpr (ENV) return {key, pt_render_env_kernel<LAYOUT, COUNT, MULTI>};
+    else return {key, pt_render_kernel<LAYOUT, COUNT, MULTI, RING>};
 }
-
-template <int LAYOUT, bool ENV, bool COUNT, bool MULTI, bool RING = false>
-void launch_k(const PtJob& job, hipStream_t st, unsigned tiles)
+template <size_t... I>
+constexpr PtKeyList<PtInstance, sizeof...(I)> pt_table(std::index_sequence<I...>)
 {
-    constexpr int wpb = waves_per_block<ENV>();
-    auto k = kernel_of<LAYOUT, ENV, COUNT, MULTI, RING>();
-    const unsigned blocks = (unsigned)std::min<long>(pt_resident_blocks(k, 64 * wpb), (tiles + wpb - 1) / wpb);
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * wpb), 0, st, job);
+    constexpr auto& k = kPtKeys.k;
+    return {{pt_instance<k[I].layout, k[I].env, k[I].count, k[I].multi, k[I].ring, k[I].ct, k[I].wide, k[I].present>()...}};
 }
-
-// Launches of at least kRingMinFrames frames run the ambient kernel's continuous ring pool (one pool
-// tail per tile instead of one per 8-frame chunk); fewer frames keep the chunked pool, whose own-lane
-// frame and lighter iteration win while there are only a few chunks.  Ring vs chunked at 1080p
-// (profiles/r03y_ab_*.jsonl): 16 spp 0.484 vs 0.462 ms, 32 spp 0.898 vs 0.890, 48 spp 1.307 vs
-// 1.316; 4K 64 spp 6.33 vs 6.74 ms; 8K 256 spp 97.9 vs 106.4 ms.
-#ifndef PT_RING_MIN
-#define PT_RING_MIN 48
-#endif
-constexpr int kRingMinFrames = PT_RING_MIN;
-
-// One-chunk ambient launches on the continuous-tiles pool (render_body_ct) when the caller provides
-// its slots for the whole grid; false: not launched (render_body then).
-template <int LAYOUT, bool ENV, bool COUNT, bool WIDE, bool PRESENT = false>
-constexpr auto ct_kernel_of()
+constexpr auto kPtTable = pt_table(std::make_index_sequence<kPtKeyCount>{});
+constexpr bool pt_table_matches()
 {
-    if constexpr (ENV) return pt_render_ct_env_kernel<LAYOUT, COUNT, PRESENT>;
-    else return pt_render_ct_kernel<LAYOUT, COUNT, WIDE ? 6 : 5, PRESENT>;
-}
-
-// *presented: the kernel wrote job.pix_out (the presenting instances: row layouts, uncounted launches)
-template <int LAYOUT, bool ENV, bool COUNT>
-bool launch_ct(const PtJob& job, hipStream_t st, unsigned tiles, bool* presented, uint32_t* ct_blocks)
-{
-    constexpr int wpb = waves_per_block<ENV>();
-    *presented = false;
-    auto k = job.ct_wide ? ct_kernel_of<LAYOUT, ENV, COUNT, true>() : ct_kernel_of<LAYOUT, ENV, COUNT, false>();
-    bool pres = false;
-    if constexpr (!COUNT && LAYOUT != PT_LAYOUT_TILED_PLANAR8) {
-        if (job.pix_out) {
-            k = job.ct_wide ? ct_kernel_of<LAYOUT, ENV, false, true, true>() : ct_kernel_of<LAYOUT, ENV, false, false, true>();
-            pres = true;
-        }
-    }
-    const unsigned blocks = (unsigned)std::min<long>(pt_resident_blocks(k, 64 * wpb), (tiles + wpb - 1) / wpb);
-    if (!job.ct_slots || (uint64_t)blocks * wpb > job.ct_waves) return false;
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * wpb), 0, st, job);
-    *presented = pres;
-    if (ct_blocks) *ct_blocks = blocks;
+    for (size_t i = 0; i < kPtKeyCount; ++i)
+        if (!(kPtTable.k[i].key == kPtKeys.k[i])) return false;
     return true;
 }
+static_assert(kPtTable.size == kPtKeys.size && pt_table_matches(), "the table holds the listed keys, in their order");
+static_assert(waves_per_block<false>() == kPickWaves && waves_per_block<true>() == kPickWaves && kChunk == kPickChunk &&
+              PT_LAYOUT_TILED_PLANAR8 == kPickTiled, "pt_kernel_pick.h's constants");
+PtResidentCache<kPtKeyCount> pt_resident;
+int resident_of(int i) { return i < 0 ? 0 : pt_resident.get((size_t)i, (const void*)kPtTable.k[i].kern, 64 * kPickWaves); }
 
-template <int LAYOUT, bool ENV>
-hipError_t launch_pools(const PtJob& job, hipStream_t st, bool count, unsigned tiles);
-
-template <int LAYOUT, bool ENV>
-hipError_t launch_t(const PtJob& job, hipStream_t st, bool count, uint32_t* ct_blocks)
+hipError_t launch_instance(int i, uint32_t grid, hipStream_t st, const PtJob& job)
 {
-    const unsigned tiles = (unsigned)((job.ncols + 7) / 8) * (unsigned)((job.nrows + 7) / 8);
-    // the continuous-tiles pool when its slots are provided (its presenting instances write
-    // job.pix_out themselves)
-    bool presented = false;
-    hipError_t e;
-    // counted launches are device jobs (pt_capi.cpp pt_count_device: the row layouts only), so the
-    // tiled layout has no counting instances
-    constexpr bool kCountable = LAYOUT != PT_LAYOUT_TILED_PLANAR8;
-    if (!kCountable && count) return hipErrorInvalidValue;
-    bool ct;
-    if constexpr (kCountable)
-        ct = count ? launch_ct<LAYOUT, ENV, true>(job, st, tiles, &presented, ct_blocks)
-                   : launch_ct<LAYOUT, ENV, false>(job, st, tiles, &presented, ct_blocks);
-    else
-        ct = launch_ct<LAYOUT, ENV, false>(job, st, tiles, &presented, ct_blocks);
-    if (ct)
-        e = hipGetLastError();
-    else
-        e = launch_pools<LAYOUT, ENV>(job, st, count, tiles);
-    if (e != hipSuccess || !job.pix_out || presented) return e;
-    // the other pools do not present: the standalone output pass over the job's rows
-    PtToneJob tj{job.buf, job.ncols, job.nrows, LAYOUT, 0, 0, job.pix_out, job.pix_xrgb ? PT_PIXEL_XRGB8 : PT_PIXEL_RGBA8, 1, 1};
-    return pt_launch_tonemap(tj, st);
-}
-
-template <int LAYOUT, bool ENV>
-hipError_t launch_pools(const PtJob& job, hipStream_t st, bool count, unsigned tiles)
-{
-    const bool multi = job.nframes > kChunk;
-    const bool ring = !ENV && job.nframes >= kRingMinFrames && job.nframes > kChunk;
-    if constexpr (LAYOUT == PT_LAYOUT_TILED_PLANAR8) {   // (no counting instances: launch_t)
-        if (ring) launch_k<LAYOUT, ENV, false, true, !ENV>(job, st, tiles);
-        else if (multi) launch_k<LAYOUT, ENV, false, true>(job, st, tiles);
-        else launch_k<LAYOUT, ENV, false, false>(job, st, tiles);
-    } else if (count) {
-        if (ring) launch_k<LAYOUT, ENV, true, true, !ENV>(job, st, tiles);
-        else if (multi) launch_k<LAYOUT, ENV, true, true>(job, st, tiles);
-        else launch_k<LAYOUT, ENV, true, false>(job, st, tiles);
-    } else {
-        if (ring) launch_k<LAYOUT, ENV, false, true, !ENV>(job, st, tiles);
-        else if (multi) launch_k<LAYOUT, ENV, false, true>(job, st, tiles);
-        else launch_k<LAYOUT, ENV, false, false>(job, st, tiles);
-    }
+    hipLaunchKernelGGL(kPtTable.k[i].kern, dim3(grid), dim3(64 * kPickWaves), 0, st, job);
     return hipGetLastError();
 }
 
@@ -2132,28 +2068,14 @@ uint32_t pt_ct_wave_floats() { return kCtWaveFloats; }
 
 int32_t pt_ct_env_waves() { return PT_ENV_WAVES; }
 
+// The slot area's waves: the largest resident grid of a continuous-tiles instance (the launch checks
+// its own grid against the job's ct_waves anyway).
 uint32_t pt_ct_resident_waves()
 {
-    static_assert(waves_per_block<false>() == waves_per_block<true>(), "one block shape for the CT kernels");
-    constexpr int wpb = waves_per_block<false>();
-    // (every continuous-tiles instance launch_ct can pick; the presenting ones have the plain ones'
-    // occupancy attributes and LDS, and launch_ct checks the grid against ct_waves anyway)
-    const int r[] = {pt_resident_blocks(pt_render_ct_kernel<PT_LAYOUT_INTERLEAVED, false, 5>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_kernel<PT_LAYOUT_INTERLEAVED, true, 5>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_kernel<PT_LAYOUT_PLANAR8, false, 5>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_kernel<PT_LAYOUT_PLANAR8, true, 5>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_kernel<PT_LAYOUT_TILED_PLANAR8, false, 5>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_kernel<PT_LAYOUT_INTERLEAVED, false, 6>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_kernel<PT_LAYOUT_INTERLEAVED, true, 6>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_kernel<PT_LAYOUT_PLANAR8, false, 6>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_kernel<PT_LAYOUT_PLANAR8, true, 6>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_kernel<PT_LAYOUT_TILED_PLANAR8, false, 6>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_env_kernel<PT_LAYOUT_INTERLEAVED, false>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_env_kernel<PT_LAYOUT_INTERLEAVED, true>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_env_kernel<PT_LAYOUT_PLANAR8, false>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_env_kernel<PT_LAYOUT_PLANAR8, true>, 64 * wpb),
-                     pt_resident_blocks(pt_render_ct_env_kernel<PT_LAYOUT_TILED_PLANAR8, false>, 64 * wpb)};
-    return (uint32_t)*std::max_element(std::begin(r), std::end(r)) * (uint32_t)wpb;
+    int r = 0;
+    for (size_t i = 0; i < kPtKeyCount; ++i)
+        if (kPtKeys.k[i].ct) r = std::max(r, resident_of((int)i));
+    return (uint32_t)r * (uint32_t)kPickWaves;
 }
 
 hipError_t pt_launch_render(const PtJob& job_in, hipStream_t st, bool count, uint32_t* ct_blocks)
@@ -2176,19 +2098,24 @@ hipError_t pt_launch_render(const PtJob& job_in, hipStream_t st, bool count, uin
     job.cam_yH = 1.0f / job.cam_H;
     job.cam_aspect = job.cam_W / job.cam_H;
     job.cam_yAspect = 1.0f / job.cam_aspect;
-    if (job.env) {
-        if (job.env_w <= 0 || job.env_h <= 0) return hipErrorInvalidValue;
-        switch (job.layout) {
-            case PT_LAYOUT_INTERLEAVED: return launch_t<PT_LAYOUT_INTERLEAVED, true>(job, st, count, ct_blocks);
-            case PT_LAYOUT_PLANAR8: return launch_t<PT_LAYOUT_PLANAR8, true>(job, st, count, ct_blocks);
-            case PT_LAYOUT_TILED_PLANAR8: return launch_t<PT_LAYOUT_TILED_PLANAR8, true>(job, st, count, ct_blocks);
-            default: return hipErrorInvalidValue;
-        }
+    if (job.env && (job.env_w <= 0 || job.env_h <= 0)) return hipErrorInvalidValue;
+    // the pick (pt_kernel_pick.h): the facts, the keys, the table entry, one launch -- the
+    // continuous-tiles pool when its slots cover the grid, else the per-tile pools
+    const PtFacts f{job.layout, job.env != nullptr, job.nframes, count, job.ct_wide != 0, job.pix_out != nullptr};
+    if (!pt_pick_valid(f)) return hipErrorInvalidValue;
+    const uint32_t tiles = (uint32_t)((job.ncols + 7) / 8) * (uint32_t)((job.nrows + 7) / 8);
+    PtKey key = pt_pick_ct_key(f);
+    int i = kPtKeys.find(key), r = resident_of(i);
+    if (r > 0 && !pt_pick_ct_takes(job.ct_slots != nullptr, job.ct_waves, (uint32_t)r, tiles)) {
+        key = pt_pick_pool_key(f);
+        r = resident_of(i = kPtKeys.find(key));
     }
-    switch (job.layout) {
-        case PT_LAYOUT_INTERLEAVED: return launch_t<PT_LAYOUT_INTERLEAVED, false>(job, st, count, ct_blocks);
-        case PT_LAYOUT_PLANAR8: return launch_t<PT_LAYOUT_PLANAR8, false>(job, st, count, ct_blocks);
-        case PT_LAYOUT_TILED_PLANAR8: return launch_t<PT_LAYOUT_TILED_PLANAR8, false>(job, st, count, ct_blocks);
-        default: return hipErrorInvalidValue;
-    }
+    if (r <= 0) return i < 0 ? hipErrorInvalidValue : hipErrorInvalidDevice;
+    const uint32_t grid = pt_pick_grid((uint32_t)r, tiles, kPickWaves);
+    if (key.ct && ct_blocks) *ct_blocks = grid;
+    const hipError_t e = launch_instance(i, grid, st, job);
+    if (e != hipSuccess || !pt_pick_tonemap_follows(job.pix_out != nullptr, key.present)) return e;
+    // the other pools do not present: the standalone output pass over the job's rows
+    const PtToneJob tj{job.buf, job.ncols, job.nrows, job.layout, 0, 0, job.pix_out, job.pix_xrgb ? PT_PIXEL_XRGB8 : PT_PIXEL_RGBA8, 1, 1};
+    return pt_launch_tonemap(tj, st);
 }

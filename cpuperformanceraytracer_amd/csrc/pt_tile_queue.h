@@ -37,8 +37,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
+#include <atomic>
 
 #include "pt_kernel.h"   // PT_NQUEUES
+#include "pt_mi355.h"    // PT_MAX_DEVICES
 #include "pt_guard.h"
 
 __device__ __forceinline__ uint32_t pt_entry_tile(uint32_t e) { return e & PT_TILE_MASK; }
@@ -265,19 +267,8 @@ struct PtTileQueue {
 // (scripts/lds_probe.hip): LDS is allocated in 1280-B granules of the CU's 160 KiB, which the API
 // does not model (it reports 5 blocks for 32001..32768 B, where 4 fit).
 constexpr int kPtLdsGranule = 1280;
-template <typename K>
-int pt_resident_blocks(K kern, int threads)
+inline int pt_resident_blocks(const void* kern, int threads, int dev)
 {
-    struct Entry {
-        const void* kern;
-        int dev, blocks;
-    };
-    static Entry cache[64];   // (kernel, device) -> resident blocks; one entry per instantiation
-    static int used = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 1024;
-    for (int i = 0; i < used; ++i)
-        if (cache[i].kern == (const void*)kern && cache[i].dev == dev) return cache[i].blocks;
     int nb = 0, cus = 0, lds_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, 0) != hipSuccess || nb <= 0) nb = 4;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
@@ -285,10 +276,26 @@ int pt_resident_blocks(K kern, int threads)
         lds_cu <= 0)
         lds_cu = 160 * 1024;
     hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, (const void*)kern) == hipSuccess && fa.sharedSizeBytes > 0) {
+    if (hipFuncGetAttributes(&fa, kern) == hipSuccess && fa.sharedSizeBytes > 0) {
         const int granules = (int)((fa.sharedSizeBytes + kPtLdsGranule - 1) / kPtLdsGranule);
         nb = std::min(nb, std::max(1, lds_cu / (granules * kPtLdsGranule)));
     }
-    if (used < 64) cache[used++] = Entry{(const void*)kern, dev, nb * cus};
     return nb * cus;
 }
+
+// The count per instance of a kernel table (pt_kernel_pick.h) and device ordinal, asked once each: a
+// slot per (table entry, ordinal below PT_MAX_DEVICES), so it neither fills up nor is searched.
+// 0: an ordinal without a slot -- the caller's launch fails (hipErrorInvalidDevice), nothing runs uncached.
+template <size_t N>
+struct PtResidentCache {
+    std::atomic<int> blocks[N][PT_MAX_DEVICES] = {};   // 0: not asked yet
+    int get(size_t i, const void* kern, int threads)
+    {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return 1024;
+        if (dev < 0 || dev >= PT_MAX_DEVICES) return 0;
+        int b = blocks[i][dev].load(std::memory_order_relaxed);
+        if (b == 0) blocks[i][dev].store(b = pt_resident_blocks(kern, threads, dev), std::memory_order_relaxed);
+        return b;
+    }
+};

@@ -35,12 +35,14 @@
 #include "pt_envcert.h"
 #include "pt_v4_default_scene.h"
 #include "pt_tile_queue.h"
+#include "pt_kernel_pick.h"
 #include "pt_guard.h"
 #include "pt_chain.h"
 #include "pt_wave.h"
 #include "pt_tonemap.h"
 #include <algorithm>
 #include <cstring>
+#include <utility>
 
 namespace {
 
@@ -1086,7 +1088,7 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_OCC void pt_v4_kernel(PtV4Job jo
 // the sky frames when they are the whole launch -- its 8-bit value (pt_tonemap.h, the default fast
 // ACES / gamma) goes to job.pix_out at the job-row address k * ncols + (X - col0), k the job's row:
 // one dword per lane, the lanes of a tile row on neighbouring addresses, as the accumulator's.  Its
-// own instances (launch_t), so the plain kernels' code and register allocation are untouched.
+// own instances (pt_kernel_pick.h), so the plain kernels' code and register allocation are untouched.
 constexpr uint32_t kV4CtWaveFloats = 2u * 64u * (uint32_t)kChunk * 3u;
 static_assert(kV4CtWaveFloats == 2u * 64u * 8u * 3u, "the slot area is the diffuse pool's (pt_ct_wave_floats)");
 enum : int {   // per-wave LDS words of the events (pt_kernel.hip kWs*)
@@ -1526,95 +1528,42 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_CT_OCC void pt_v4_ct_kernel(PtV4
     }
 }
 
-template <int ENV, int LAYOUT>
-hipError_t launch_t(const PtV4Job& j, const PtV4Scene& sc, hipStream_t st, bool count, bool* presented,
-                    uint32_t* ct_blocks_out)
+// The instance table: entry i is the kernel of kPtV4Keys[i] (pt_kernel_pick.h).  v4_instance makes an
+// entry's key and its pointer from the same template arguments.
+using V4Kernel = void (*)(PtV4Job, PtV4Scene);
+struct V4Instance {
+    PtV4Key key;
+    V4Kernel kern;
+};
+template <bool CT, int ENV, int LAYOUT, bool COUNT, bool DEF, int FEXP, bool DFL, bool PRESENT>
+constexpr V4Instance v4_instance()
 {
-    const int tiles = ((j.ncols + 7) / 8) * ((j.nrows + 7) / 8);
-    const dim3 block(64 * kWaves);
-    *presented = false;
-    // persistent grid: the resident blocks, at most one tile per wave.  The continuous-tiles kernel
-    // when the caller provides its slots for the whole grid and the launch holds >= 4 full chunks
-    // (8 frames x tile) per wave, else the per-tile pool kernel.  Measured (round 4, 5-wave CT vs
-    // per-tile): 1080p 32 spp 1.257 vs 1.320 ms (51 chunks per wave), 4K 8 spp 1.308 vs 1.328 (25),
-    // 1080p 8 spp 0.3602 vs 0.3589 (6), 1 spp 0.133 vs 0.115 (one item per pixel and chunk: the
-    // chunk events, claim and fold, dominate); round 5, the 6-wave CT kernel: 1080p 8 spp (5.3 chunks
-    // per wave) 0.3591 vs 0.3602.
-    const auto go_ct = [&](auto ct_kern) {   // true: the continuous-tiles kernel took the launch
-        const long ct_blocks = std::min<long>(pt_resident_blocks(ct_kern, 64 * kWaves), (tiles + kWaves - 1) / kWaves);
-        const uint64_t ct_waves = (uint64_t)ct_blocks * kWaves;
-        if (!(j.ct_slots && ct_waves <= j.ct_waves && j.nframes >= kChunk &&
-              (j.ct_force || (uint64_t)j.nframes * (uint64_t)tiles >= 4ull * kChunk * ct_waves)))
-            return false;
-        hipLaunchKernelGGL(ct_kern, dim3((unsigned)ct_blocks), block, 0, st, j, sc);
-        if (ct_blocks_out) *ct_blocks_out = (uint32_t)ct_blocks;
-        return true;
-    };
-    const auto go = [&](auto kern, auto ct_kern) {
-        if (go_ct(ct_kern)) return;
-        const long blocks = std::min<long>(pt_resident_blocks(kern, 64 * kWaves), (tiles + kWaves - 1) / kWaves);
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), block, 0, st, j, sc);
-    };
-    if constexpr (LAYOUT == PT_LAYOUT_TILED_PLANAR8) {   // the presenting instances (pt_launch_v4: one frame)
-        if (j.pix_out && !count) {
-            auto k = pt_v4_kernel<ENV, LAYOUT, false, true, 1, true, true>;
-            const long blocks = std::min<long>(pt_resident_blocks(k, 64 * kWaves), (tiles + kWaves - 1) / kWaves);
-            hipLaunchKernelGGL(k, dim3((unsigned)blocks), block, 0, st, j, sc);
-            *presented = true;
-            return hipGetLastError();
-        }
-    } else if (j.pix_out && !count) {
-        // the presenting instances of a device job (pt_launch_v4: job-row pixels, fast exp, the default
-        // tonemap pair): the continuous-tiles twins of the default scene's default-flags instance and
-        // of the generic scene's -- a launch the continuous-tiles kernel does not take renders plain
-        // below and the caller converts (*presented stays false)
-        const bool took = j.default_scene ? go_ct(pt_v4_ct_kernel<ENV, LAYOUT, false, true, 1, true, true>)
-                                          : go_ct(pt_v4_ct_kernel<ENV, LAYOUT, false, false, 1, false, true>);
-        if (took) {
-            *presented = true;
-            return hipGetLastError();
-        }
-    }
-    // The tiled layout is the drop-in's (pt_capi.cpp pt_render_opt_v4 and its work-queue entries): one
-    // frame per call (NUM_SAMPLES_PER_FRAME = 1), never counted (counted launches are device jobs, the
-    // row layouts only) -- so only the per-tile pool's uncounted instances exist for it.
-    if constexpr (LAYOUT == PT_LAYOUT_TILED_PLANAR8) {
-        if (count || j.nframes >= kChunk) return hipErrorInvalidValue;
-        const auto tile_go = [&](auto kern) {
-            const long blocks = std::min<long>(pt_resident_blocks(kern, 64 * kWaves), (tiles + kWaves - 1) / kWaves);
-            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), block, 0, st, j, sc);
-        };
-        if (j.default_scene) {
-            if (j.fast_exp && j.random_jitter && j.rejection) tile_go(pt_v4_kernel<ENV, LAYOUT, false, true, 1, true>);
-            else if (j.fast_exp) tile_go(pt_v4_kernel<ENV, LAYOUT, false, true, 1>);
-            else tile_go(pt_v4_kernel<ENV, LAYOUT, false, true, 0>);
-        } else {
-            if (j.fast_exp) tile_go(pt_v4_kernel<ENV, LAYOUT, false, false, 1>);
-            else tile_go(pt_v4_kernel<ENV, LAYOUT, false, false, 0>);
-        }
-    } else if (j.default_scene) {
-        if (count) go(pt_v4_kernel<ENV, LAYOUT, true, true, 2>, pt_v4_ct_kernel<ENV, LAYOUT, true, true, 2>);
-        else if (j.fast_exp && j.random_jitter && j.rejection)
-            go(pt_v4_kernel<ENV, LAYOUT, false, true, 1, true>, pt_v4_ct_kernel<ENV, LAYOUT, false, true, 1, true>);
-        else if (j.fast_exp) go(pt_v4_kernel<ENV, LAYOUT, false, true, 1>, pt_v4_ct_kernel<ENV, LAYOUT, false, true, 1>);
-        else go(pt_v4_kernel<ENV, LAYOUT, false, true, 0>, pt_v4_ct_kernel<ENV, LAYOUT, false, true, 0>);
-    } else {
-        if (count) go(pt_v4_kernel<ENV, LAYOUT, true, false, 2>, pt_v4_ct_kernel<ENV, LAYOUT, true, false, 2>);
-        else if (j.fast_exp) go(pt_v4_kernel<ENV, LAYOUT, false, false, 1>, pt_v4_ct_kernel<ENV, LAYOUT, false, false, 1>);
-        else go(pt_v4_kernel<ENV, LAYOUT, false, false, 0>, pt_v4_ct_kernel<ENV, LAYOUT, false, false, 0>);
-    }
-    return hipGetLastError();
+    constexpr PtV4Key key{ENV, LAYOUT, COUNT, DEF, FEXP, DFL, PRESENT, CT};
+    if constexpr (CT) return {key, pt_v4_ct_kernel<ENV, LAYOUT, COUNT, DEF, FEXP, DFL, PRESENT>};
+    else return {key, pt_v4_kernel<ENV, LAYOUT, COUNT, DEF, FEXP, DFL, PRESENT>};
 }
-
-template <int ENV>
-hipError_t launch_env(const PtV4Job& j, const PtV4Scene& sc, hipStream_t st, bool count, bool* presented, uint32_t* ct_blocks)
+template <size_t... I>
+constexpr PtKeyList<V4Instance, sizeof...(I)> v4_table(std::index_sequence<I...>)
 {
-    switch (j.layout) {
-        case PT_LAYOUT_INTERLEAVED: return launch_t<ENV, PT_LAYOUT_INTERLEAVED>(j, sc, st, count, presented, ct_blocks);
-        case PT_LAYOUT_PLANAR8: return launch_t<ENV, PT_LAYOUT_PLANAR8>(j, sc, st, count, presented, ct_blocks);
-        case PT_LAYOUT_TILED_PLANAR8: return launch_t<ENV, PT_LAYOUT_TILED_PLANAR8>(j, sc, st, count, presented, ct_blocks);
-        default: return hipErrorInvalidValue;
-    }
+    constexpr auto& k = kPtV4Keys.k;
+    return {{v4_instance<k[I].ct, k[I].env, k[I].layout, k[I].count, k[I].def, k[I].fexp, k[I].dfl, k[I].present>()...}};
+}
+constexpr auto kV4Table = v4_table(std::make_index_sequence<kPtV4KeyCount>{});
+constexpr bool v4_table_matches()
+{
+    for (size_t i = 0; i < kPtV4KeyCount; ++i)
+        if (!(kV4Table.k[i].key == kPtV4Keys.k[i])) return false;
+    return true;
+}
+static_assert(kV4Table.size == kPtV4Keys.size && v4_table_matches(), "the table holds the listed keys, in their order");
+static_assert(kWaves == kPickWaves && kChunk == kPickChunk && PT_LAYOUT_TILED_PLANAR8 == kPickTiled &&
+              PT_V4_ENV_NONE_ == 0 && PT_V4_ENV_CUBEMAP_ == 2, "pt_kernel_pick.h's constants");
+PtResidentCache<kPtV4KeyCount> v4_resident;
+
+hipError_t launch_instance(int i, uint32_t grid, hipStream_t st, const PtV4Job& j, const PtV4Scene& sc)
+{
+    hipLaunchKernelGGL(kV4Table.k[i].kern, dim3(grid), dim3(64 * kWaves), 0, st, j, sc);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -1633,32 +1582,36 @@ hipError_t pt_launch_v4(const PtV4Job& j_in, const PtV4Scene& sc, hipStream_t st
     *presented = false;
     if (ct_blocks) *ct_blocks = 0;
     if (j_in.ncols <= 0 || j_in.nrows <= 0 || j_in.nframes <= 0) return hipSuccess;
-    // the fused output stage (j.pix_out) runs in the presenting instances only, uncounted, with fast
-    // exp and the default fast ACES / gamma:
-    //  - the drop-in's calls (DemofoxRenderOptV4: the tiled layout, one frame -- the per-tile pool
-    //    kernel, full-image pixel rows), the default scene and sampling flags;
-    //  - device jobs (pt_v4_render_device_present: a row layout, job-row pixels, pix_rows) that the
-    //    continuous-tiles kernel takes (launch_t decides: *presented), the default scene with the
-    //    default sampling flags or a generic scene.
     PtV4Job j = j_in;
     if (j.sky.nrects > PT_V4_SKYWIN_MAX) return hipErrorInvalidValue;
-    // the DEF instances carry the default camera as literals: any other camera runs the generic ones
-    const float cam_default[4] = {0.0f, 0.0f, 40.0f, 1.0f}, cam[4] = {j.cam_pos[0], j.cam_pos[1], j.cam_pos[2], j.cam_dist};
-    if (memcmp(cam, cam_default, sizeof(cam)) != 0) j.default_scene = 0;
-    const bool tiled = j.layout == PT_LAYOUT_TILED_PLANAR8;
-    const bool tone = j.fast_exp && j.pix_fast_tone && !count;
-    const bool dflt = j.default_scene && j.random_jitter && j.rejection;
-    if (j.pix_out && !(tone && (j.pix_rows ? !tiled && j.nframes >= kChunk && (dflt || !j.default_scene)
-                                           : tiled && j.nframes < kChunk && dflt)))
-        j.pix_out = nullptr;
     if (sc.nquads < 0 || sc.nspheres < 0 || sc.nquads + sc.nspheres > PT_V4_MAX_OBJECTS) return hipErrorInvalidValue;
     if (j.env_mode != PT_V4_ENV_NONE_ && (!j.env || j.env_w <= 0 || j.env_h <= 0)) return hipErrorInvalidValue;
     if (count && !j.counters) return hipErrorInvalidValue;
     if (!j.queue || (j.order && (!j.units || !j.nunits))) return hipErrorInvalidValue;
-    switch (j.env_mode) {
-        case PT_V4_ENV_NONE_: return launch_env<PT_V4_ENV_NONE_>(j, sc, st, count, presented, ct_blocks);
-        case PT_V4_ENV_EQUIRECT_: return launch_env<PT_V4_ENV_EQUIRECT_>(j, sc, st, count, presented, ct_blocks);
-        case PT_V4_ENV_CUBEMAP_: return launch_env<PT_V4_ENV_CUBEMAP_>(j, sc, st, count, presented, ct_blocks);
-        default: return hipErrorInvalidValue;
+    // the pick (pt_kernel_pick.h): the facts, the keys, the table entry, one launch
+    const PtV4Facts f{j.env_mode, j.layout, j.nframes, count, j.default_scene != 0, pt_v4_camera_is_default(j.cam_pos, j.cam_dist),
+                      j.fast_exp != 0, j.random_jitter != 0, j.rejection != 0, j.pix_out != nullptr, j.pix_rows != 0,
+                      j.pix_fast_tone != 0};
+    if (!pt_pick_v4_valid(f)) return hipErrorInvalidValue;
+    const PtV4Norm n = pt_pick_v4_normalise(f);
+    j.default_scene = n.def;
+    if (!n.present) j.pix_out = nullptr;
+    const uint32_t tiles = (uint32_t)((j.ncols + 7) / 8) * (uint32_t)((j.nrows + 7) / 8);
+    const auto resident = [](int i) { return i < 0 ? 0 : v4_resident.get((size_t)i, (const void*)kV4Table.k[i].kern, 64 * kWaves); };
+    const PtV4CtKey ck = pt_pick_v4_ct_key(f, n);
+    if (ck.any) {
+        const int i = kPtV4Keys.find(ck.key), r = resident(i);
+        if (r <= 0) return i < 0 ? hipErrorInvalidValue : hipErrorInvalidDevice;
+        if (pt_pick_v4_ct_takes(j.ct_slots != nullptr, j.ct_waves, (uint32_t)r, tiles, j.nframes, j.ct_force != 0)) {
+            const uint32_t grid = pt_pick_grid((uint32_t)r, tiles, kWaves);
+            if (ct_blocks) *ct_blocks = grid;
+            *presented = ck.key.present;
+            return launch_instance(i, grid, st, j, sc);
+        }
     }
+    const PtV4Key tk = pt_pick_v4_tile_key(f, n);
+    const int i = kPtV4Keys.find(tk), r = resident(i);
+    if (r <= 0) return i < 0 ? hipErrorInvalidValue : hipErrorInvalidDevice;
+    *presented = tk.present;
+    return launch_instance(i, pt_pick_grid((uint32_t)r, tiles, kWaves), st, j, sc);
 }

@@ -5,8 +5,8 @@ The kernels are templates over layout (interleaved / planar8 / tiled-planar8), e
 launches, launch shape (continuous-tiles pool at 5 or 6 waves per SIMD, per-tile pool: one chunk,
 MULTI chunks, the RING pool), the fused output stage, and for v4 the env mode, scene (the default
 InitializeScene geometry or an Add*ToScene one) and sampling / exp flags.  Each case below picks one
-instance with the switches that select it (pt_kernel.hip launch_t / launch_ct / launch_pools,
-pt_v4.hip launch_t) on a small image, renders through the public entry point that reaches it, and
+instance with the switches that select it (csrc/pt_kernel_pick.h: pt_pick_ct_key / pt_pick_pool_key,
+pt_pick_v4_ct_key / pt_pick_v4_tile_key, looked up in the instance tables) on a small image, renders through the public entry point that reaches it, and
 compares with oracle/pt_oracle.c or oracle/pt_oracle_v4.c.  DESIGN.md §3d lists the instances;
 scripts/gpu_coverage.sh runs this suite under rocprofv3 --kernel-trace and
 tests/test_kernel_coverage.py checks that the launched set covers every instance in the library.
