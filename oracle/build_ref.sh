@@ -2,8 +2,8 @@
 # oracle/build_ref.sh -- TEST INFRASTRUCTURE ONLY.
 #
 # Builds the reference's own scalar path tracer (unmodified, compiled where it lies under
-# /root/reference) into oracle/_ref/ so it can (a) generate the golden fixtures in tests/golden
-# and (b) serve as the "reference" CPU baseline in bench.py.  Nothing from the reference is
+# /root/reference) and, at the end of this script, its v4 renderer's lines 1-1556 into oracle/_ref/
+# so it can (a) generate the golden fixtures in tests/golden and (b) serve as the "reference" CPU baseline in bench.py.  Nothing from the reference is
 # copied into the repository: the one generated header (a selection of mathlib.h's own scalar
 # lines, see below) lives in a temporary directory that is deleted on exit, and only the
 # compiled binary/.so land in oracle/_ref/ (git-ignored).
@@ -101,3 +101,83 @@ $CXX -std=c++17 -O2 -w -I"$REF" "$HERE/ref_hdr.cpp" -o "$OUT/ref_hdr" -lm
 # WriteImage's encoder (output stage): the reference's vendored stb_image_write.h, where it lies
 $CXX -std=c++17 -O2 -w -I"$REF" "$HERE/ref_bmp.cpp" -o "$OUT/ref_bmp" -lm
 echo "build_ref.sh: built $OUT/libref_scalar.so, $OUT/ref_scalar, $OUT/ref_scalar_b8, $OUT/ref_env, $OUT/ref_hdr and $OUT/ref_bmp"
+
+# --- the v4 renderer (demofox_path_tracing_optimization_v4.cpp) ------------------------------------
+# The reference's own v4 lines 1-1556 (everything above the Win32 thread pool), compiled where
+# mathlib.h, mathutils.h and texture.cpp lie, inside oracle/ref_v4.cpp's driver and behind
+# oracle/ref_v4_shim.h (every substitution is listed in that header).  The extracted lines, the two
+# Win32 stub headers (our text) and the flag-variant copies of global_preprocessor_flags.h live in
+# $GEN only.  `-I-` keeps "global_preprocessor_flags.h" from being found next to the including file,
+# so a variant's copy is the one every header sees.
+# global_preprocessor_flags.h defines its switches unconditionally, so each variant is a temporary
+# copy with ONLY the named lines' values changed; the script checks that exactly those lines differ
+# and records the diff and both sha256s in oracle/_ref/v4_flags.json (tests/golden/make_golden_v4.py
+# copies it into tests/golden/manifest.json).
+V4="$REF/demofox_path_tracing_optimization_v4.cpp"
+FLAGS_H="$REF/global_preprocessor_flags.h"
+if [ ! -f "$V4" ] || [ ! -f "$FLAGS_H" ]; then
+    echo "build_ref.sh: the reference's v4 file is not present -- skipping ref_v4 (committed fixtures are used)" >&2
+    exit 0
+fi
+if ! grep -qw avx2 /proc/cpuinfo 2>/dev/null || ! grep -qw fma /proc/cpuinfo 2>/dev/null; then
+    echo "build_ref.sh: this CPU lacks AVX2/FMA -- skipping ref_v4 (committed fixtures are used)" >&2
+    exit 0
+fi
+V4GEN="$GEN/v4"
+mkdir -p "$V4GEN/stubs"
+awk 'NR<=1556' "$V4" > "$V4GEN/ref_v4_body.inc"
+: > "$V4GEN/stubs/intrin.h"
+printf '%s\n' '#pragma once' 'typedef void* HANDLE;' 'typedef unsigned long DWORD;' 'typedef void* LPVOID;' \
+    '#define WINAPI' > "$V4GEN/stubs/windows.h"
+V4FLAGS="-std=c++17 -O2 -mavx2 -mfma -ffp-contract=off -fno-operator-names -w"
+# variant name, then line:MACRO:new-value for every changed line (global_preprocessor_flags.h :56-66)
+V4_VARIANTS=(
+    "shipped"
+    "cubemap 57:USE_ENV_CUBEMAP:1"
+    "bilinear 66:USE_RANDOM_JITTER_TEXTURE_SAMPLING:0"
+    "angle 65:USE_UNIT_VECTOR_REJECTION_SAMPLING:0"
+    "noenv 56:USE_ENV_MAP:0"
+    "exactexp 64:USE_FAST_APPROXIMATE_EXP:0"
+    "exactout 63:USE_FAST_APPROXIMATE_ACES_TONEMAP:0 62:USE_FAST_APPROXIMATE_GAMMA:0"
+    "noaccum 60:ACCUMULATE_FRAMES:0"
+)
+V4_JSON_ARGS=()
+V4_BUILT=""
+for spec in "${V4_VARIANTS[@]}"; do
+    set -- $spec
+    name=$1; shift
+    D="$V4GEN/$name"
+    mkdir -p "$D"
+    cp "$FLAGS_H" "$D/global_preprocessor_flags.h"
+    nedits=0
+    for e in "$@"; do
+        IFS=: read -r ln macro val <<< "$e"
+        sed -i "${ln}s/^#define ${macro} [01]\(\r\{0,1\}\)\$/#define ${macro} ${val}\1/" "$D/global_preprocessor_flags.h"
+        nedits=$((nedits + 1))
+    done
+    NDIFF=$(diff "$FLAGS_H" "$D/global_preprocessor_flags.h" | grep -c '^[<>]' || true)
+    if [ "$NDIFF" != "$((2 * nedits))" ]; then
+        echo "build_ref.sh: v4 variant $name did not change exactly its $nedits flag line(s) ($NDIFF diff lines)" >&2
+        exit 1
+    fi
+    diff "$FLAGS_H" "$D/global_preprocessor_flags.h" | tr -d '\r' > "$D/flags.diff" || true
+    $CXX $V4FLAGS -D'__declspec(x)=__attribute__((x))' -D'align(n)=aligned(n)' \
+        -DREF_V4_BODY="\"$V4GEN/ref_v4_body.inc\"" \
+        -I"$D" -I"$V4GEN/stubs" -I"$HERE" -I- -I"$D" -I"$V4GEN/stubs" -I"$HERE" -I"$REF" \
+        "$HERE/ref_v4.cpp" -o "$OUT/ref_v4_$name" -lm 2> "$D/cc.log" || { cat "$D/cc.log" >&2; exit 1; }
+    V4_JSON_ARGS+=("$name" "$D/global_preprocessor_flags.h" "$D/flags.diff" "$*")
+    V4_BUILT="$V4_BUILT ref_v4_$name"
+done
+python3 - "$V4" "$FLAGS_H" "${V4_JSON_ARGS[@]}" > "$OUT/v4_flags.json" <<'PY'
+import hashlib, json, sys
+h = lambda p: hashlib.sha256(open(p, "rb").read()).hexdigest()
+v4, flags, rest = sys.argv[1], sys.argv[2], sys.argv[3:]
+out = {"file": "global_preprocessor_flags.h", "sha256_original": h(flags),
+       "v4_file": "demofox_path_tracing_optimization_v4.cpp", "v4_lines": "1-1556", "v4_sha256": h(v4), "variants": {}}
+for name, patched, diff, edits in zip(rest[0::4], rest[1::4], rest[2::4], rest[3::4]):
+    out["variants"][name] = {
+        "lines": {e.split(":")[0]: "#define %s %s" % tuple(e.split(":")[1:]) for e in edits.split()},
+        "sha256_patched": h(patched), "diff": open(diff).read()}
+print(json.dumps(out, indent=1))
+PY
+echo "build_ref.sh: built$V4_BUILT in $OUT"

@@ -22,8 +22,9 @@
  *   atan2_ps / asin_ps / sincos_ps (SVML, MSVC-only)              -> glibc atan2f / asinf / sinf+cosf
  * so against a run of the reference on a particular x86 CPU a pixel may differ in low bits
  * ("parity unpinned" for those terms); the HIP kernel must match THIS restatement bit
- * for bit.  The reference file itself is Win32 code (work queue, Interlocked*, SVML) and is not
- * built here.
+ * for bit.  With the same three substitutions (oracle/ref_v4_shim.h) the reference's own lines
+ * 1-1556 are compiled by oracle/build_ref.sh, and this restatement equals their images bit for
+ * bit (tests/test_v4_ref_pin.py, tests/golden/v4_ref_*.npz).
  *
  * Reference quirks reproduced on purpose:
  *   - AddMaterialToScene stores albedo.x in all three albedo channels (v4 :1370-1372);

@@ -1,11 +1,13 @@
 """CPU checks of the v4 oracle (oracle/pt_oracle_v4.c), the checker for the v4 GPU kernel.
 
-The reference's v4 file (demofox_path_tracing_optimization_v4.cpp) is Win32 + SVML code and
-cannot be built here, so these pin the restatement piecewise: its RNG against the scalar oracle's
+Whole images of the restatement are pinned to the reference's own v4 lines
+(demofox_path_tracing_optimization_v4.cpp :1-1556 compiled with GCC behind oracle/ref_v4_shim.h) by
+tests/test_v4_ref_pin.py.  These older checks pin it piecewise: its RNG against the scalar oracle's
 wang hash (itself pinned to the reference's goldens), Randomf3201_ps / the camera / the env lookups
 against independent numpy + libm restatements of mathutils.h and texture.cpp, the scene tables of
 InitializeScene, and the renderer's structural invariants (row shards, frame splits, pixel
-independence).  Parity of the whole v4 image against a reference run is unpinned.
+independence).  What stays unpinned after the whole-image pin: the rcp / rsroot / SVML stand-ins and
+MSVC-versus-GCC code generation.
 """
 from __future__ import annotations
 

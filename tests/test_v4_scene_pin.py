@@ -1,7 +1,7 @@
 """Pins the v4 oracle's default scene to the reference's own InitializeScene (v4 :1403-1496).
 
-The v4 renderer cannot be built here (Win32 / MSVC / SVML), so its outputs are "parity unpinned"
-(DESIGN.md §2b).  Its scene, though, is literal data in the reference source: this test reads that
+The v4 renderer's images are pinned by tests/test_v4_ref_pin.py (the reference's own lines compiled
+with GCC).  Its scene is also literal data in the reference source: this test reads that
 source as text and checks every number of the oracle's scene description against it: the quad vertices
 with the scene translation (0, 0, 10) of SCENE 1 (v4 :697, :1406-1408) added where the reference
 adds it (not to the striped background, :1431-1434), the seven spheres of the loop (:1469-1494) and
