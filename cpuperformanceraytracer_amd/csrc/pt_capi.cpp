@@ -88,6 +88,7 @@ struct Sched {
 constexpr int kSchedSlots = 16;
 constexpr int kBands = 4;   // PT_FLAG_PIN_HOST: row bands of a pipelined frame
 constexpr unsigned kQueueRing = 256;       // tile-queue ring slots (reuse across streams is event-ordered)
+constexpr unsigned kViewRing = 4;          // view tables of pt_v4_render_device_views (Dev::views)
 // launches per schedule build (g.sched_rebuild; PT_MI355_SCHED_REBUILD): 256 -- a build restarts the
 // chained overlap and costs a one-workgroup kernel (~57 us at 1080p); 3-round A/B of chained steps vs 64
 // (profiles/r06/r06zl_*): c2 0.2160 vs 0.2189 ms, c4 0.4582 vs 0.4633, v4 0.3286 vs 0.3313
@@ -134,6 +135,19 @@ struct Dev {
     size_t dgather_cap = 0;
     hipEvent_t ev_gather = nullptr;     // recorded after this device's rows were stored
     bool peer_root = false;             // this device may store into the root's memory
+    // views launches (pt_v4_render_device_views): a ring of kViewRing view tables.  A launch fills the
+    // next slot's page-locked host table, copies it to the slot's device table on its stream and records
+    // the slot's event after its kernel; a slot is reused only once that event has completed (the host
+    // waits for it -- four launches back, normally long done).  So a table that an earlier asynchronous
+    // launch may still be reading, on this stream or another, is never written, and no stream is made
+    // to wait for another.
+    struct ViewSlot {
+        PtV4View* host = nullptr;       // PT_V4_MAX_VIEWS records, page-locked
+        PtV4View* dev = nullptr;
+        hipEvent_t done = nullptr;
+        bool pending = false;           // done has been recorded
+    } views[kViewRing];
+    unsigned views_next = 0;
     // chained launches (pt_render_device_chain, launch_chain): consecutive launches of one geometry
     // alternate on two streams of the library's and overlap on the GPU
     struct Chain {
@@ -204,6 +218,8 @@ struct State {
     // that it fires -- the error path's own GPU test (tests/test_gpu_state.py)
     uint32_t ring_guard_cap = ~0u;
     int32_t v4_ct_force = 0;   // PT_MI355_V4_CT=1 (read by pt_init): PtV4Job::ct_force (tests)
+    uint32_t v4_views_grid = 0;   // PT_MI355_V4_VIEWS_GRID=<blocks> (read by pt_init): PtV4Views::grid_cap (tests: a
+                                  // grid of few waves, so that each wave takes tiles of several views)
     uint32_t ct_back_pct = 20;   // PT_MI355_BACK (read by pt_init): PtJob::ct_back_pct (0: none)
     bool back_set = false;       // PT_MI355_BACK given: the occupancy timing keeps it
     uint32_t ct_waves = 0;       // PT_MI355_CT_WAVES (read by pt_init): 5 or 6 waves per SIMD; 0 (default):
@@ -371,6 +387,7 @@ const char* guard_name(uint32_t id)
         case PT_G_SCHED_UNIT: return "schedule builder: unit index out of range";
         case PT_G_RECORD: return "item record slot >= 64";
         case PT_G_QUEUE_GROUP: return "queue group out of range";
+        case PT_G_VIEW: return "views launch: view index beyond the view table";
         case PT_G_CAM_INDEX: return "camera-hit cache record outside the geometry's tiles";
         case PT_G_CAM_RECORD: return "a traced camera hit differs from its cached record; value: tile * 64 + lane";
         case PT_G_CHAIN_WAIT: return "chained launch: the previous launch's tile never became ready; value: the tile | its epoch's lag "
@@ -677,6 +694,8 @@ int chain_join(Dev& dv, hipStream_t st)
     return PT_OK;
 }
 
+int use_queue_slot(Dev& dv, hipStream_t st, LaunchSched* ls);
+
 // key.split: the schedule builder's tile split factor (pt_launch_schedule; 0: whole tiles).  *sched_st:
 // the stream that identifies the geometry's schedule (launch_chain: the caller's stream, which may be
 // the null stream; nullptr: st).
@@ -708,6 +727,13 @@ int use_sched(Dev& dv, const SchedKey& key, hipStream_t st, LaunchSched* ls, con
         }
         ++s->launches;
     }
+    return use_queue_slot(dv, st, ls);
+}
+
+// The tile-queue fields of a launch on `st` (use_sched's second half; a views launch, which has no
+// schedule, takes only these).
+int use_queue_slot(Dev& dv, hipStream_t st, LaunchSched* ls)
+{
     // Ring slots are used in order.  Each render kernel zeroes the NEXT slot's counters at its start,
     // so a launch after a launched kernel on the same stream finds its slot zero.  After a launch on
     // another stream that slot may still be being zeroed: it is skipped (its next user waits for that
@@ -1438,12 +1464,17 @@ int v4_rebuild()
 
 // The sky window of the current (scene, camera) (pt_v4_skywin.h): host arithmetic, built on first use
 // after a scene edit or a camera change.  PT_MI355_V4_SKYWIN=0: no window (A/B timing, tests).
+void v4_sky_window_of(const float position[3], PtV4SkyWin* out)   // the current scene seen from `position`
+{
+    static const bool off = getenv("PT_MI355_V4_SKYWIN") && !strcmp(getenv("PT_MI355_V4_SKYWIN"), "0");
+    if (off) *out = PtV4SkyWin{-1, {}};
+    else pt_v4_skywin_build(g.v4desc.nquads, g.v4desc.quad, g.v4desc.nspheres, g.v4desc.sphere, position, out);
+}
+
 const PtV4SkyWin& v4_sky_window()
 {
     if (!g.v4sky_ready) {
-        static const bool off = getenv("PT_MI355_V4_SKYWIN") && !strcmp(getenv("PT_MI355_V4_SKYWIN"), "0");
-        if (off) g.v4sky = PtV4SkyWin{-1, {}};
-        else pt_v4_skywin_build(g.v4desc.nquads, g.v4desc.quad, g.v4desc.nspheres, g.v4desc.sphere, g.v4cam.position, &g.v4sky);
+        v4_sky_window_of(g.v4cam.position, &g.v4sky);
         g.v4sky_ready = true;
     }
     return g.v4sky;
@@ -1563,6 +1594,12 @@ void free_dev(Dev& dv)
     if (dv.dtone_out) (void)hipFree(dv.dtone_out);
     if (dv.dgather) (void)hipFree(dv.dgather);
     if (dv.ev_gather) (void)hipEventDestroy(dv.ev_gather);
+    for (Dev::ViewSlot& v : dv.views) {
+        if (v.pending) (void)hipEventSynchronize(v.done);   // (its launch may run on a caller's stream)
+        if (v.done) (void)hipEventDestroy(v.done);
+        if (v.dev) (void)hipFree(v.dev);
+        if (v.host) (void)hipHostFree(v.host);
+    }
     for (Sched& sc : dv.sched)
         if (sc.used) free_sched(sc);
     for (hipEvent_t& e : dv.queue_event)
@@ -1706,6 +1743,7 @@ int pt_init(const pt_config* cfg)
                                                         : kSchedRebuildDefault;
     g.unit_mult = getenv("PT_MI355_UNIT_MULT") ? std::max<uint32_t>(1u, (uint32_t)strtoul(getenv("PT_MI355_UNIT_MULT"), nullptr, 10)) : 2u;
     g.v4_ct_force = getenv("PT_MI355_V4_CT") && !strcmp(getenv("PT_MI355_V4_CT"), "1");
+    g.v4_views_grid = getenv("PT_MI355_V4_VIEWS_GRID") ? (uint32_t)strtoul(getenv("PT_MI355_V4_VIEWS_GRID"), nullptr, 10) : 0u;
     g.ct_back_pct = 20;
     g.back_set = false;
     if (const char* bk = getenv("PT_MI355_BACK")) g.ct_back_pct = (uint32_t)strtoul(bk, nullptr, 10), g.back_set = true;
@@ -2335,18 +2373,30 @@ void pt_v4_default_camera(pt_v4_camera* c)
     c->fov_degrees = 90.0f;  // c_FOVDegrees, v4 :20
 }
 
-int pt_v4_set_camera(const pt_v4_camera* c)
+// The camera check of pt_v4_set_camera and of every view of pt_v4_render_device_views (view >= 0: the
+// message names it); *dist: camera.Distance.
+static int v4_check_camera(const pt_v4_camera* c, float* dist, int view)
 {
-    if (!c) return fail(PT_EINVAL, "null v4 camera");
+    char who[32] = "";
+    if (view >= 0) snprintf(who, sizeof(who), "view %d: ", view);
     for (int k = 0; k < 3; ++k)
         if (!std::isfinite(c->position[k]) || std::fabs(c->position[k]) > 1024.0f)
-            return fail(PT_EINVAL, "camera position[%d] = %g is not finite or beyond +-1024", k, (double)c->position[k]);
+            return fail(PT_EINVAL, "%scamera position[%d] = %g is not finite or beyond +-1024", who, k, (double)c->position[k]);
     if (!std::isfinite(c->fov_degrees) || !(c->fov_degrees > 0.0f && c->fov_degrees < 180.0f))
-        return fail(PT_EINVAL, "fov_degrees %g outside (0, 180)", (double)c->fov_degrees);
-    const float dist = v4_camera_distance(c->fov_degrees);
-    if (!(std::isnormal(dist) && dist > 0.0f))
-        return fail(PT_EINVAL, "fov_degrees %g gives the camera distance %g, not a finite positive normal f32",
-                    (double)c->fov_degrees, (double)dist);
+        return fail(PT_EINVAL, "%sfov_degrees %g outside (0, 180)", who, (double)c->fov_degrees);
+    *dist = v4_camera_distance(c->fov_degrees);
+    if (!(std::isnormal(*dist) && *dist > 0.0f))
+        return fail(PT_EINVAL, "%sfov_degrees %g gives the camera distance %g, not a finite positive normal f32", who,
+                    (double)c->fov_degrees, (double)*dist);
+    return PT_OK;
+}
+
+int pt_v4_set_camera(const pt_v4_camera* c)
+{
+    int rc;
+    float dist = 0.0f;
+    if (!c) return fail(PT_EINVAL, "null v4 camera");
+    if ((rc = v4_check_camera(c, &dist, -1))) return rc;
     g.v4cam = *c;
     g.v4cam_dist = dist;
     g.v4sky_ready = false;
@@ -2522,6 +2572,92 @@ int pt_v4_render_device_chain(const pt_device_job* dj, void* stream)
     DeviceGuard guard;
     if ((rc = ensure_init()) || (rc = v4_device_job(dj, &j)) || (rc = dev_of(dj->buf, &dv))) return rc;
     return launch_chain(*dv, j, (hipStream_t)stream);
+}
+
+// A batch of views in one launch (include/pt_mi355.h; pt_v4.h PtV4Views).  Everything is checked before
+// the first HIP call.  The view table goes through the device's ring (Dev::views); the launch is a plain,
+// unscheduled one of the per-tile pool's views instances -- it joins (ends) a live chain and takes a
+// tile-queue ring slot like every plain launch, and touches no geometry's schedule state.
+int pt_v4_render_device_views(const pt_device_job* dj, const pt_v4_camera* cams, int32_t nviews, uint32_t* pixels,
+                              int32_t format, void* stream)
+{
+    int rc;
+    if (!dj) return fail(PT_EINVAL, "null device job");
+    {
+        pt_device_job geo = *dj;   // (the geometry / frame checks, as v4_device_job's)
+        geo.use_env = 0;
+        PtJob unused;
+        if ((rc = device_job(&geo, &unused))) return rc;
+    }
+    if (!cams) return fail(PT_EINVAL, "null camera array");
+    if (nviews < 1 || nviews > PT_V4_MAX_VIEWS) return fail(PT_EINVAL, "nviews %d outside [1, %d]", nviews, PT_V4_MAX_VIEWS);
+    if (pixels && format != PT_PIXEL_RGBA8 && format != PT_PIXEL_XRGB8) return fail(PT_EINVAL, "unknown pixel format %d", format);
+    const uint64_t view_tiles = (uint64_t)((dj->width + 7) / 8) * (uint64_t)((dj->nrows + 7) / 8);
+    if (view_tiles * (uint64_t)nviews > PT_TILE_MASK)
+        return fail(PT_EINVAL, "%d views x %llu tiles exceed the tile queue's %u entries", nviews, (unsigned long long)view_tiles,
+                    PT_TILE_MASK);
+    std::vector<float> dist((size_t)nviews);
+    for (int32_t v = 0; v < nviews; ++v)
+        if ((rc = v4_check_camera(&cams[v], &dist[(size_t)v], v))) return rc;
+    if (dj->nframes == 0 || dj->nrows == 0) return PT_OK;   // nothing to render
+
+    PtV4Job j;
+    Dev* dvp = nullptr;
+    DeviceGuard guard;
+    if ((rc = ensure_init()) || (rc = v4_device_job(dj, &j)) || (rc = dev_of(dj->buf, &dvp)) || (rc = use_dev(*dvp))) return rc;
+    Dev& dv = *dvp;
+    hipStream_t st = (hipStream_t)stream;
+    // the job's own camera fields are not read by the views instances
+    memset(j.cam_pos, 0, sizeof(j.cam_pos));
+    j.cam_dist = 0.0f;
+    j.sky = PtV4SkyWin{-1, {}};
+    j.default_scene = 0;
+    if (j.env_mode != PT_V4_ENV_NONE) j.env = dv.denv;
+    j.err = dv.derr;
+    // the render kernel writes the pixels with the default tonemap pair; any other pair: a second pass
+    const bool fused = pixels && g.v4cfg.fast_aces && g.v4cfg.fast_gamma;
+    j.pix_xrgb = format == PT_PIXEL_XRGB8;
+
+    Dev::ViewSlot& vs = dv.views[dv.views_next++ % kViewRing];
+    const size_t table_bytes = (size_t)PT_V4_MAX_VIEWS * sizeof(PtV4View);
+    if (!vs.host && hipHostMalloc(&vs.host, table_bytes, hipHostMallocDefault) != hipSuccess) {
+        vs.host = nullptr;
+        return fail(PT_ENOMEM, "hipHostMalloc(view table) failed");
+    }
+    if (!vs.dev && hipMalloc(&vs.dev, table_bytes) != hipSuccess) {
+        vs.dev = nullptr;
+        return fail(PT_ENOMEM, "hipMalloc(view table) failed");
+    }
+    if (!vs.done) HIP_TRY(hipEventCreateWithFlags(&vs.done, hipEventDisableTiming));
+    if (vs.pending) {   // the slot's previous launch (kViewRing launches back) still reads the table: wait for it
+        HIP_TRY(hipEventSynchronize(vs.done));
+        vs.pending = false;
+    }
+    for (int32_t v = 0; v < nviews; ++v) {
+        PtV4View& r = vs.host[v];
+        memcpy(r.cam_pos, cams[v].position, sizeof(r.cam_pos));
+        r.cam_dist = dist[(size_t)v];
+        v4_sky_window_of(cams[v].position, &r.sky);
+    }
+    HIP_TRY(hipMemcpyAsync(vs.dev, vs.host, (size_t)nviews * sizeof(PtV4View), hipMemcpyHostToDevice, st));
+
+    LaunchSched ls;
+    if ((rc = chain_join(dv, st)) || (rc = use_queue_slot(dv, st, &ls))) return rc;
+    j.queue = ls.queue;
+    j.queue_next = ls.queue_next;
+    const PtV4Views va{vs.dev, nviews, fused ? pixels : nullptr, g.v4_views_grid};
+    hipError_t e = pt_launch_v4_views(j, g.v4scene, va, st);
+    if (e != hipSuccess) return fail(PT_EHIP, "v4 views launch failed: %s", hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(vs.done, st));
+    vs.pending = true;
+    if ((rc = queue_done(dv, ls.slot, st, true))) return rc;
+    if (pixels && !fused) {
+        // (the slices lie back to back: one image of nviews x nrows rows in either row layout)
+        const PtToneJob tj = tone_job(j.buf, j.ncols, j.nrows * nviews, j.layout, 0, 0, pixels, format);
+        e = pt_launch_tonemap(tj, st);
+        if (e != hipSuccess) return fail(PT_EHIP, "tonemap launch failed: %s", hipGetErrorString(e));
+    }
+    return PT_OK;
 }
 
 int pt_v4_count_device(const pt_device_job* dj, void* stream, pt_work_counts* out)

@@ -108,6 +108,7 @@ enum PtGuardId : uint32_t {
     PT_G_CHAIN_WAIT = 13,   // a chained launch polled 2^21 times (>= 2 s) for the previous launch's tile (every build)
     PT_G_CAM_INDEX = 14,    // a camera-hit cache record outside the geometry's tiles
     PT_G_CAM_RECORD = 15,   // a counted launch traced a camera hit that differs from its cached record (every build)
+    PT_G_VIEW = 16,         // a views launch: a tile entry's view index beyond the view table
 };
 
 // Tile queues: one counter per XCD group, 128 B apart (PT_QUEUE_WORDS u32 per launch).

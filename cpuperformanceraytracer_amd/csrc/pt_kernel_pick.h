@@ -242,3 +242,24 @@ constexpr PtKeyList<PtV4Key, kPtV4KeyCount> pt_v4_key_list()
     return l;
 }
 constexpr PtKeyList<PtV4Key, kPtV4KeyCount> kPtV4Keys = pt_v4_key_list();
+
+// ---- v4 views (pt_v4.hip pt_v4_views_kernel <env, layout, fexp>) ----
+// A batch of views runs the per-tile pool's generic form only: uncounted, a row layout, the sampling
+// flags and the pixel output at run time.  A list of its own: kPtV4Keys stays what one-camera jobs reach.
+struct PtV4ViewsKey {
+    int env, layout, fexp;
+    constexpr bool operator==(const PtV4ViewsKey& o) const { return env == o.env && layout == o.layout && fexp == o.fexp; }
+};
+constexpr bool pt_pick_v4_views_valid(int env, int layout) { return env >= 0 && env < 3 && layout >= 0 && layout < kPickTiled; }
+constexpr PtV4ViewsKey pt_pick_v4_views_key(int env, int layout, bool fast_exp) { return {env, layout, fast_exp ? 1 : 0}; }
+constexpr size_t kPtV4ViewsKeyCount = 3 * 2 * 2;
+constexpr PtKeyList<PtV4ViewsKey, kPtV4ViewsKeyCount> pt_v4_views_key_list()
+{
+    PtKeyList<PtV4ViewsKey, kPtV4ViewsKeyCount> l{};
+    size_t n = 0;
+    for (int env = 0; env < 3; ++env)
+        for (int layout = 0; layout < kPickTiled; ++layout)
+            for (int fexp = 1; fexp >= 0; --fexp) l.k[n++] = {env, layout, fexp};
+    return l;
+}
+constexpr PtKeyList<PtV4ViewsKey, kPtV4ViewsKeyCount> kPtV4ViewsKeys = pt_v4_views_key_list();

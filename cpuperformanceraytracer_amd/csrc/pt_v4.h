@@ -121,3 +121,27 @@ bool pt_v4_is_default_geometry(const PtV4Scene& s);                // geometry =
 hipError_t pt_v4_set_chain_polls(uint32_t polls);
 hipError_t pt_launch_v4(const PtV4Job& job, const PtV4Scene& scene, hipStream_t stream, bool count,
                         bool* presented = nullptr, uint32_t* ct_blocks = nullptr);
+
+// ---- a batch of views in one launch (pt_v4_render_device_views; pt_v4.hip pt_v4_views_kernel) ----
+// The per-tile pool's tile queue spans nviews views of one job geometry: entry e is tile e % T of view
+// e / T (T = the job's tiles).  What differs per view -- the camera and the sky window of (scene,
+// camera) -- is a record of a device table (job and scene already fill most of the 4 KiB of kernel
+// arguments; 1024 records are 212 KiB); the view also selects the accumulator slice, job.buf + view *
+// nrows * width * 3, and the pixel slice, pix + view * nrows * width.  The job's own cam_pos, cam_dist
+// and sky are not read.
+struct PtV4View {
+    float cam_pos[3];   // camera.Position
+    float cam_dist;     // camera.Distance (the host's 1 / tanf, as pt_v4_set_camera's)
+    PtV4SkyWin sky;     // pt_v4_skywin_build for (scene, cam_pos); nrects -1: no window
+};
+static_assert(sizeof(PtV4View) == 16 + sizeof(PtV4SkyWin) && sizeof(PtV4View) % 4 == 0, "a view record is whole dwords");
+struct PtV4Views {
+    const PtV4View* table;   // device memory, nviews records, read-only while the launch runs
+    int32_t nviews;
+    uint32_t* pix;           // nviews x nrows x width packed pixels (the default fast ACES / gamma,
+                             // job.pix_xrgb), or nullptr: none
+    uint32_t grid_cap;       // test knob: at most this many blocks (0: the resident grid)
+};
+// The generic instances (ENV x row layout x FEXP), unscheduled (job.order, units, cost: nullptr), a
+// plain launch.  job.ncols == job.width, job.col0 == 0 (a device job).
+hipError_t pt_launch_v4_views(const PtV4Job& job, const PtV4Scene& scene, const PtV4Views& views, hipStream_t stream);

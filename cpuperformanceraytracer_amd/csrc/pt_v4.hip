@@ -526,6 +526,45 @@ struct V4Cam {
     }
 };
 
+// The camera of one view of a views launch (pt_v4.h PtV4Views): V4Cam<false>'s operations on the view's
+// record instead of the job's fields.  take() runs when a wave takes a tile -- a persistent wave crosses
+// from one view's tiles to the next's, so nothing of the previous tile's camera may survive it: the
+// position, the distance and the window's rectangle count are reloaded there, and the rectangles are
+// read through `rec` at every sky test.  The record is read through the constant address space: the
+// address is wave-uniform (the table pointer is a kernel argument, the view index comes from the queue
+// entry in scalar registers), so these are scalar loads, and the table is read-only while the launch runs.
+struct V4ViewCam {
+    typedef const __attribute__((address_space(4))) PtV4View* Rec;
+    Rec rec = nullptr;
+    float px = 0.0f, py = 0.0f, pz = 0.0f, dist = 1.0f;
+    int32_t nrects = -1;
+    __device__ __forceinline__ void take(const PtV4View* table, uint32_t view)
+    {
+        rec = (Rec)(table + view);
+        px = rec->cam_pos[0];
+        py = rec->cam_pos[1];
+        pz = rec->cam_pos[2];
+        dist = rec->cam_dist;
+        nrects = rec->sky.nrects;
+    }
+    __device__ __forceinline__ V3 ray(float tx, float ty) const   // (V4Cam<false>::ray)
+    {
+        return normalize(v3(tx, ty, -dist) - v3(0.0f, 0.0f, 0.0f));
+    }
+    __device__ __forceinline__ V3 position() const { return v3(px, py, pz); }
+    __device__ __forceinline__ bool has_sky() const { return nrects >= 0; }
+    __device__ __forceinline__ bool sky(V3 d) const   // pt_v4_skywin_sky on the record's window
+    {
+        const float nz = -d.z;
+        bool s = nrects >= 0 && nz > 0.0f && d.x == d.x && d.y == d.y;
+        for (int i = 0; i < nrects; ++i) {
+            const float r0 = rec->sky.rect[i][0], r1 = rec->sky.rect[i][1], r2 = rec->sky.rect[i][2], r3 = rec->sky.rect[i][3];
+            s = s && (d.x < r0 * nz || d.x > r1 * nz || d.y < r2 * nz || d.y > r3 * nz);
+        }
+        return s;
+    }
+};
+
 // TestSceneTrace :700-718: quads in order, then spheres (object index = material index).
 // DEF: the reference's InitializeScene, geometry as instruction literals (pt_v4_default_scene.h,
 // generated from pt_v4_build_scene and checked by tests/test_oracle_v4.py); otherwise the scene
@@ -797,7 +836,9 @@ __device__ __forceinline__ void v4_segment(const PtV4Job& job, const PtV4Scene& 
 #ifdef PT_V4_WAVES   // A/B builds: force the occupancy (waves per SIMD)
 #define PT_V4_OCC __attribute__((amdgpu_waves_per_eu(PT_V4_WAVES, PT_V4_WAVES)))
 #define PT_V4_CT_OCC PT_V4_OCC
+#define PT_V4_VIEWS_OCC PT_V4_OCC
 #else
+#define PT_V4_VIEWS_OCC __attribute__((amdgpu_waves_per_eu(5)))   // the views instances: as the plain render instances
 // render instances: at least 5 waves per SIMD (<= 96 VGPRs; the exact-exp instance needs 97
 // otherwise and compiles spill-free at 96); the diagnostic COUNT instances are left unconstrained
 #define PT_V4_OCC __attribute__((amdgpu_waves_per_eu(COUNT ? 1 : 5)))
@@ -829,246 +870,33 @@ __device__ __forceinline__ void v4_present(const PtV4Job& job, int X, int Y, V3 
             pt_tone::pack<true, true>(acc.x, acc.y, acc.z, job.pix_xrgb != 0);
 }
 
+// The per-tile pool's body is pt_v4_tile_pool.inc, the text of both kernels below: pt_v4_kernel (VIEWS
+// false) and pt_v4_views_kernel (VIEWS: a batch of views, pt_v4.h PtV4Views -- the queue holds ntiles x
+// nviews entries, and the entry's view selects the camera record, the accumulator slice and the pixel
+// slice).  An include, not a function: with the body one call away, behind references to the kernel
+// arguments, the compiler scheduled pt_v4_kernel's instances differently; as the kernel's own text --
+// everything VIEWS adds under `if constexpr` -- they compile to the code they had.  Each kernel declares
+// VIEWS, `cam` and `va` for it.
 template <int ENV, int LAYOUT, bool COUNT, bool DEF, int FEXP, bool DFL = false, bool PRESENT = false>
 __global__ __launch_bounds__(64 * kWaves) PT_V4_OCC void pt_v4_kernel(PtV4Job job, PtV4Scene sc)
 {
-    __shared__ float s_col[kWaves][kChunk * 64 * 3];
-    __shared__ PtV4Mat s_mat[PT_V4_MAX_OBJECTS];
-    __shared__ float4 s_sc[DEF ? pt_v4_default::kSpheres : 1];   // default scene: sphere centre, radius
-    __shared__ MatX s_mx[PT_V4_MAX_OBJECTS];                        // per-material constants (mat_consts)
-    constexpr bool DEFER = ENV != PT_V4_ENV_NONE_;
-    __shared__ float4 s_qd[DEFER ? kWaves : 1][DEFER ? kEnvQ : 1];   // env dir, rng
-    __shared__ float4 s_qt[DEFER ? kWaves : 1][DEFER ? kEnvQ : 1];   // throughput, colour slot
-    for (int t = threadIdx.x; t < PT_V4_MAX_OBJECTS * 17; t += 64 * kWaves)
-        reinterpret_cast<float*>(s_mat)[t] = reinterpret_cast<const float*>(sc.mat)[t];
-    __syncthreads();
-    if (threadIdx.x < PT_V4_MAX_OBJECTS) s_mx[threadIdx.x] = mat_consts(s_mat[threadIdx.x]);
-    if (DEF && threadIdx.x < pt_v4_default::kSpheres) {
-        const float* c = pt_v4_default::kSphere[threadIdx.x];
-        s_sc[threadIdx.x] = make_float4(c[0], c[1], c[2], c[3]);
-    }
-    __syncthreads();
-
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    pt_queue_zero_next(job.queue_next);   // (pt_tile_queue.h)
-    const int tiles_x = (job.ncols + 7) >> 3;
-    const int ntiles = tiles_x * ((job.nrows + 7) >> 3);
-    float* const col = s_col[wv];
-    const size_t cs = (LAYOUT == PT_LAYOUT_INTERLEAVED) ? 1u : 8u;
-    const Tex tex{job.env, job.env_w, job.env_h};
-    const bool random = DFL || job.random_jitter != 0, rejection = DFL || job.rejection != 0;
-    const int B = job.num_bounces;
-    const float W = (float)job.width, H = (float)job.height;
-    const float rW = rcp(W), rH = rcp(H);
+    constexpr bool VIEWS = false;
+    constexpr PtV4Views va{nullptr, 0, nullptr, 0u};   // (named in discarded statements only)
     const V4Cam<DEF> cam(job);   // camera.Distance, camera.Position (InitializeCamera :1500-1501)
-    unsigned long long n_seg = 0, n_esc = 0, n_slots = 0, n_fb = 0, n_sky = 0;
+#include "pt_v4_tile_pool.inc"
+}
 
-    // persistent waves: 8x8 tiles from the launch's queue (pt_tile_queue.h), longest first when the
-    // geometry has a schedule
-    constexpr uint32_t kNone = PtTileQueue<kWaves>::kNone;
-    PtTileQueue<kWaves> tq(job.queue, job.order, job.units, job.nunits, (uint32_t)ntiles, wv);
-    uint32_t tile = kNone, next_tile = kNone;
-    tile = tq.first(job.err);   // (the whole wave: uniform, scalar registers)
-    tile = __builtin_amdgcn_readfirstlane(tile);
-    while (tile != kNone) {
-    // (this kernel's schedules hold whole tiles: pt_capi.cpp v4_launch)
-    const int tcol = ((int)pt_entry_tile(tile) % tiles_x) * 8, trow = ((int)pt_entry_tile(tile) / tiles_x) * 8;
-    uint32_t tile_work = 1;   // pool iterations of this tile (the schedule's cost)
-
-    // this lane's pixel (phase C) and its accumulator
-    const int px = job.col0 + tcol + (lane & 7), pr = trow + (lane >> 3);
-    const bool pvalid = (tcol + (lane & 7)) < job.ncols && pr < job.nrows;
-    float* acc_p = nullptr;
-    V3 acc = v3(0.0f, 0.0f, 0.0f);
-    if (pvalid) {
-        // compact layouts index the buffer row; the tiled layout indexes the full image (global row)
-        const int orow = LAYOUT == PT_LAYOUT_TILED_PLANAR8 ? job.row_start + pr * job.row_stride : pr;
-        acc_p = job.buf + out_index<LAYOUT>(job, px, orow);
-        if (job.accumulate) acc = v3(acc_p[0], acc_p[cs], acc_p[2 * cs]);   // (:1233: only to blend)
-    }
-
-    for (int c0 = 0; c0 < job.nframes; c0 += kChunk) {
-        const int nf = std::min(kChunk, job.nframes - c0);
-        const int total = 64 * nf;
-        int next = 0;      // wave-uniform
-        int item = -1;     // this lane's (pixel, frame) sample, -1 = none
-        V3 pos, dir, T, ret;
-        uint32_t rng = 0;
-        int bounce = 0;
-        int qn = 0;   // queued misses (DEFER), wave-uniform
-        // a deferred miss: env(d) with the rng state r, fma'd with throughput t into colour slot k
-        auto resolve = [&](V3 d, uint32_t r, V3 t, int k) {
-            V3 amb = v3(0.0f, 0.0f, 0.0f);
-            if (ENV == PT_V4_ENV_EQUIRECT_) amb = equirect(tex, d, random, r);
-            if (ENV == PT_V4_ENV_CUBEMAP_) amb = cubemap(tex, d, random, r);
-            float* o = col + k;
-            const V3 rt = v3(fma_(amb.x, t.x, o[0]), fma_(amb.y, t.y, o[1]), fma_(amb.z, t.z, o[2]));   // :787
-            o[0] = fma_(rt.x, 1.0f, 0.0f);   // :1127
-            o[1] = fma_(rt.y, 1.0f, 0.0f);
-            o[2] = fma_(rt.z, 1.0f, 0.0f);
-        };
-        // evaluate the queued misses [0, m), one per lane
-        auto drain = [&](int m) {
-            if (lane < m) {
-                const float4 a = s_qd[DEFER ? wv : 0][lane], b = s_qt[DEFER ? wv : 0][lane];
-                resolve(v3(a.x, a.y, a.z), __builtin_bit_cast(uint32_t, a.w), v3(b.x, b.y, b.z),
-                        __builtin_bit_cast(int, b.w));
-            }
-        };
-        for (;;) {
-            // hand out items to idle lanes, in lane order
-            const bool need = item < 0;
-            const unsigned long long m = pt_ballot(need);
-            if (need) {
-                const int it = next + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                if (it < total) {
-                    // frame-major (pixel-major, a pixel's frames on neighbouring lanes, measured
-                    // 1-2.5 % slower here: the jittered camera rays share no bounce-0 origin)
-                    const int p = it & 63, f = it >> 6;
-                    const int X = job.col0 + tcol + (p & 7), rb = trow + (p >> 3);
-                    if ((tcol + (p & 7)) < job.ncols && rb < job.nrows) {
-                        item = f * 64 + p;   // colour slot order (phase C)
-                        // mainImage :1092-1130
-                        const int Y = job.row_start + rb * job.row_stride;
-                        const uint32_t frame = job.frame_first + (uint32_t)(c0 + f);
-                        const int fyi = job.height - 1 - Y;
-                        // 24 x 24-bit products: X, fyi, frame < 2^24 (C ABI), low words = the u32 products
-                        rng = 1u | (__umul24((uint32_t)X, 1973u) + __umul24((uint32_t)fyi, 9277u) + __umul24(frame, 26699u));
-                        const float jx = randf(rng) - 0.5f;
-                        const float jy = randf(rng) - 0.5f;
-                        const float tx = fma_(((float)X + jx) * rW, 2.0f, -1.0f);
-                        float ty = fma_(((float)fyi + jy) * rH, 2.0f, -1.0f);
-                        ty = ty * (rW * H);
-                        dir = cam.ray(tx, ty);
-                        pos = cam.position();
-                        T = v3(1.0f, 1.0f, 1.0f);
-                        ret = v3(0.0f, 0.0f, 0.0f);
-                        bounce = 0;
-                    }
-                }
-            }
-            next += __builtin_popcountll(m);
-            if (pt_ballot(item >= 0) == 0ull) break;
-            ++tile_work;
-            if (COUNT) n_slots += 64;
-            bool queued = false;   // DEFER: this lane's item missed and goes to the queue
-            int qslot = 0;
-            // default scene: when every busy lane traces a camera ray that leaves the scene's
-            // silhouette (sky_ray_v4), the wave skips TestSceneTrace -- the reference's miss
-            // (the slope test runs only in iterations where every busy lane is at bounce 0: a wave-
-            // uniform branch, instead of the test on every lane in every iteration)
-            // any other (scene, camera): the same with its sky window (pt_v4_skywin.h), when it has one
-            bool all_sky = false;
-            if (cam.has_sky() && pt_ballot(item >= 0 && bounce != 0) == 0)
-                all_sky = pt_ballot(item >= 0 && !cam.sky(dir)) == 0;
-            if (item >= 0) {
-                bool done = false;
-                v4_segment<ENV, COUNT, DEF, FEXP, DFL>(job, sc, s_mat, s_mx, s_sc, tex, random, rejection, B, all_sky, pos,
-                                                       dir, T, ret, rng, bounce, done, queued, n_seg, n_esc, n_fb, n_sky);
-                if (done) {
-                    const int p = item & 63, f = item >> 6;
-                    qslot = (f * 64 + p) * 3;
-                    float* o = col + qslot;
-                    if (DEFER && queued) {   // ret so far; the drain adds the env term
-                        o[0] = ret.x;
-                        o[1] = ret.y;
-                        o[2] = ret.z;
-                    } else {
-                        // mainImage :1127: fmadd(color, 1/c_numRendersPerFrame, 0)
-                        o[0] = fma_(ret.x, 1.0f, 0.0f);
-                        o[1] = fma_(ret.y, 1.0f, 0.0f);
-                        o[2] = fma_(ret.z, 1.0f, 0.0f);
-                    }
-                    item = -1;
-                }
-            }
-            if (DEFER) {
-                const unsigned long long qm = pt_ballot(queued);
-                const int nq = __builtin_popcountll(qm);
-                const V3 ed = ENV == PT_V4_ENV_EQUIRECT_ ? v3(-dir.x, dir.y, -dir.z) : dir;
-                if (qn + nq > kEnvQ) {
-                    // overflow: one env pass over the whole wave -- the new misses in their own lanes,
-                    // the other lanes each take one queued miss (the top `take` entries, so the rest
-                    // stay in place).  At least kEnvQ + 1 lanes busy (min(qn + nq, 64)); the drain-or-
-                    // new-batch choice this replaces ran 24-48 of the 64.
-                    const int take = std::min(qn, 64 - nq);
-                    const int r = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(~qm >> 32),
-                                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)~qm, 0u));
-                    V3 d = ed, t = T;
-                    uint32_t rr = rng;
-                    int k = qslot;
-                    bool act = queued;
-                    if (!queued && r < take) {
-                        const int e = qn - take + r;
-                        const float4 a = s_qd[DEFER ? wv : 0][DEFER ? e : 0], b = s_qt[DEFER ? wv : 0][DEFER ? e : 0];
-                        d = v3(a.x, a.y, a.z);
-                        rr = __builtin_bit_cast(uint32_t, a.w);
-                        t = v3(b.x, b.y, b.z);
-                        k = __builtin_bit_cast(int, b.w);
-                        act = true;
-                    }
-                    if (act) resolve(d, rr, t, k);
-                    qn -= take;
-                } else {
-                    if (queued) {
-                    const int k = qn + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(qm >> 32),
-                                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)qm, 0u));
-                        s_qd[DEFER ? wv : 0][k] = make_float4(ed.x, ed.y, ed.z, __builtin_bit_cast(float, rng));
-                        s_qt[DEFER ? wv : 0][k] = make_float4(T.x, T.y, T.z, __builtin_bit_cast(float, qslot));
-                    }
-                    qn += nq;
-                }
-            }
-        }
-        if (DEFER && qn > 0) drain(qn);
-        if (c0 + kChunk >= job.nframes) next_tile = tq.next(job.err);   // the last pool is done
-        // all radiance of this chunk is in LDS (written by lanes of this wave)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (pvalid) {
-            for (int f = 0; f < nf; ++f) {
-                const float* c = col + (f * 64 + lane) * 3;
-                if (job.accumulate) {   // ACCUMULATE_FRAMES 1: fmadd(blend_factor, color - last, last) :1233-1241
-                    const float bf = rcp((float)(job.frame_first + (uint32_t)(c0 + f)) + 1.0f);   // :1200
-                    acc = v3(fma_(bf, c[0] - acc.x, acc.x), fma_(bf, c[1] - acc.y, acc.y), fma_(bf, c[2] - acc.z, acc.z));
-                } else {                // ACCUMULATE_FRAMES 0: the frame's colour is stored (:1245-1250)
-                    acc = v3(c[0], c[1], c[2]);
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    if (job.nframes <= 0) next_tile = tq.next(job.err);   // no chunk ran
-    if (pvalid) {
-        acc_p[0] = acc.x;
-        acc_p[cs] = acc.y;
-        acc_p[2 * cs] = acc.z;
-        v4_present<PRESENT>(job, px, job.row_start + pr * job.row_stride, acc);
-    }
-    if (job.cost && lane == 0) pt_record_cost(job.cost, tile, (uint32_t)ntiles, tile_work);
-    tile = __builtin_amdgcn_readfirstlane(next_tile);
-    }
-    tq.report(job.err);   // (a schedule entry outside the launch, pt_tile_queue.h)
-    if (COUNT) {
-        // per-lane counts summed over the wave by lane 0's atomics
-        for (int off = 32; off > 0; off >>= 1) {
-            n_seg += __shfl_down(n_seg, off);
-            n_esc += __shfl_down(n_esc, off);
-            n_fb += __shfl_down(n_fb, off);
-            n_sky += __shfl_down(n_sky, off);
-        }
-        if (lane == 0) {
-            atomicAdd(&job.counters[0], n_seg);
-            atomicAdd(&job.counters[2], n_esc);
-            atomicAdd(&job.counters[3], n_slots);
-            atomicAdd(&job.counters[4], n_fb);
-            atomicAdd(&job.counters[5], n_sky);
-        }
-    }
+// A batch of views in one launch (pt_v4_render_device_views, pt_v4.h PtV4Views): the per-tile pool over
+// the tiles of every view.  The generic form only -- the literal-geometry instances carry the default
+// camera -- with the sampling flags and the pixel output at run time: ENV x row layout x FEXP, 12
+// instances of its own (pt_kernel_pick.h kPtV4ViewsKeys), at the plain instances' 5 waves per SIMD.
+template <int ENV, int LAYOUT, int FEXP>
+__global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_views_kernel(PtV4Job job, PtV4Scene sc, PtV4Views va)
+{
+    static_assert(LAYOUT != PT_LAYOUT_TILED_PLANAR8, "views run the generic, uncounted row-layout form");
+    constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false;
+    V4ViewCam cam;   // the tile's view's camera (take(), when the wave takes a tile)
+#include "pt_v4_tile_pool.inc"
 }
 
 // ---- continuous tiles (CT): the v4 pool without per-tile tails ----------------------------------
@@ -1566,6 +1394,21 @@ hipError_t launch_instance(int i, uint32_t grid, hipStream_t st, const PtV4Job& 
     return hipGetLastError();
 }
 
+// The views instances: entry i is the kernel of kPtV4ViewsKeys[i], as above.
+using V4ViewsKernel = void (*)(PtV4Job, PtV4Scene, PtV4Views);
+struct V4ViewsInstance {
+    PtV4ViewsKey key;
+    V4ViewsKernel kern;
+};
+template <size_t... I>
+constexpr PtKeyList<V4ViewsInstance, sizeof...(I)> v4_views_table(std::index_sequence<I...>)
+{
+    constexpr auto& k = kPtV4ViewsKeys.k;
+    return {{V4ViewsInstance{k[I], pt_v4_views_kernel<k[I].env, k[I].layout, k[I].fexp>}...}};
+}
+constexpr auto kV4ViewsTable = v4_views_table(std::make_index_sequence<kPtV4ViewsKeyCount>{});
+PtResidentCache<kPtV4ViewsKeyCount> v4_views_resident;
+
 }  // namespace
 
 hipError_t pt_v4_set_chain_polls(uint32_t polls)
@@ -1614,4 +1457,23 @@ hipError_t pt_launch_v4(const PtV4Job& j_in, const PtV4Scene& sc, hipStream_t st
     if (r <= 0) return i < 0 ? hipErrorInvalidValue : hipErrorInvalidDevice;
     *presented = tk.present;
     return launch_instance(i, pt_pick_grid((uint32_t)r, tiles, kWaves), st, j, sc);
+}
+
+hipError_t pt_launch_v4_views(const PtV4Job& j, const PtV4Scene& sc, const PtV4Views& va, hipStream_t st)
+{
+    if (j.ncols <= 0 || j.nrows <= 0 || j.nframes <= 0) return hipSuccess;
+    if (!va.table || va.nviews < 1 || j.col0 != 0 || j.ncols != j.width) return hipErrorInvalidValue;
+    if (sc.nquads < 0 || sc.nspheres < 0 || sc.nquads + sc.nspheres > PT_V4_MAX_OBJECTS) return hipErrorInvalidValue;
+    if (j.env_mode != PT_V4_ENV_NONE_ && (!j.env || j.env_w <= 0 || j.env_h <= 0)) return hipErrorInvalidValue;
+    if (!j.queue || j.order || j.units || j.cost || j.counters) return hipErrorInvalidValue;   // unscheduled, uncounted
+    if (!pt_pick_v4_views_valid(j.env_mode, j.layout)) return hipErrorInvalidValue;
+    const uint64_t tiles = (uint64_t)((j.ncols + 7) / 8) * (uint64_t)((j.nrows + 7) / 8) * (uint64_t)va.nviews;
+    if (tiles > PT_TILE_MASK) return hipErrorInvalidValue;   // (a queue entry carries view * tiles + tile)
+    const int i = kPtV4ViewsKeys.find(pt_pick_v4_views_key(j.env_mode, j.layout, j.fast_exp != 0));
+    const int r = i < 0 ? 0 : v4_views_resident.get((size_t)i, (const void*)kV4ViewsTable.k[i].kern, 64 * kWaves);
+    if (r <= 0) return i < 0 ? hipErrorInvalidValue : hipErrorInvalidDevice;
+    uint32_t grid = pt_pick_grid((uint32_t)r, (uint32_t)tiles, kWaves);
+    if (va.grid_cap && grid > va.grid_cap) grid = va.grid_cap;
+    hipLaunchKernelGGL(kV4ViewsTable.k[i].kern, dim3(grid), dim3(64 * kWaves), 0, st, j, sc, va);
+    return hipGetLastError();
 }

@@ -228,6 +228,33 @@ def render_v4_device_present(buf, pixels, width: int, height: int, *, frame_firs
             "pt_v4_render_device_present")
 
 
+def render_v4_device_views(buf, cameras, width: int, height: int, *, frame_first: int, nframes: int, num_bounces: int = 8,
+                           row_start: int = 0, row_stride: int = 1, nrows: int | None = None,
+                           layout: int = N.PT_LAYOUT_INTERLEAVED, use_env: bool = False, pixels=None,
+                           pixel_format: int = N.PT_PIXEL_RGBA8, stream=None) -> None:
+    """A batch of views in one launch (pt_v4_render_device_views): `cameras` is a sequence of (position,
+    fov_degrees) as renderer.v4_camera takes them, `buf` a contiguous f32 device tensor of at least
+    V x nrows x width x 3 elements (e.g. shaped [V, nrows, W, 3]) whose slice v ends bit for bit as
+    v4_camera(*cameras[v]) + render_v4_device on it would leave it.  pixels: an optional 32-bit tensor of
+    V x nrows x width words, each slice equal to tonemap_device on its accumulator slice.  The camera of
+    v4_camera and the v4 frame counter are neither read nor changed.  Asynchronous on `stream`."""
+    nrows = height if nrows is None else nrows
+    cams = [(tuple(float(x) for x in pos), float(fov)) for pos, fov in cameras]
+    nviews = len(cams)
+    if any(len(pos) != 3 for pos, _ in cams):
+        raise N.PtError(N.PT_EINVAL, "render_v4_device_views", "a camera position has three components")
+    if not 1 <= nviews <= N.PT_V4_MAX_VIEWS:
+        raise N.PtError(N.PT_EINVAL, "render_v4_device_views", f"{nviews} cameras outside [1, {N.PT_V4_MAX_VIEWS}]")
+    # (_job checks the tensor against nrows: the batch as one job of V x nrows rows, then the job's own rows)
+    job = _job(buf, width, height, row_start, row_stride, nviews * nrows, frame_first, nframes, num_bounces, layout, use_env)
+    job.nrows = nrows
+    if pixels is not None:
+        _check_pixels(pixels, nviews * nrows * width, buf)
+    arr = (N.PtV4Camera * nviews)(*[N.PtV4Camera((ctypes.c_float * 3)(*pos), fov) for pos, fov in cams])
+    N.check(N.load().pt_v4_render_device_views(ctypes.byref(job), arr, nviews, pixels.data_ptr() if pixels is not None else None,
+                                               pixel_format, _stream(stream)), "pt_v4_render_device_views")
+
+
 def count_v4_device(buf, width: int, height: int, *, frame_first: int, nframes: int, num_bounces: int = 8,
                     row_start: int = 0, row_stride: int = 1, nrows: int | None = None,
                     layout: int = N.PT_LAYOUT_INTERLEAVED, use_env: bool = False, stream=None) -> dict:

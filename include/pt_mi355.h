@@ -336,6 +336,32 @@ int pt_v4_render_device_chain(const pt_device_job* job, void* hip_stream);
  * converts in a second pass on hip_stream.  Not chained: a plain launch, it ends a live chain.
  * NULL pixels or an unknown format: PT_EINVAL.  Async on hip_stream. */
 int pt_v4_render_device_present(const pt_device_job* job, uint32_t* pixels, int32_t format, void* hip_stream);
+/* A batch of views of the current scene in ONE launch: nviews cameras, one job geometry.  For many
+ * small views (turntables, thumbnails, stacks for a torch pipeline) one launch fills the GPU where a
+ * launch per view leaves it nearly idle (INTEGRATION.md "Batches of views").
+ *   job     every view uses the job's width, height, row_start, row_stride, nrows, layout, frame_first,
+ *           nframes, num_bounces and use_env.  job->buf holds nviews accumulators back to back: view v
+ *           starts at buf + v * nrows * width * 3 floats.
+ *   result  after the launch, view v's slice is bit for bit what pt_v4_set_camera(&cams[v]) followed by
+ *           pt_v4_render_device on that slice would leave -- for the current scene (InitializeScene's or
+ *           one edited through Add*ToScene) and pt_v4_config.
+ *   pixels  NULL, or device memory of nviews x nrows x width u32 in the same view order: each slice's
+ *           packed values (PT_PIXEL_*), equal to pt_tonemap_device on that slice with the config's
+ *           fast_aces / fast_gamma.  With the default pair (1, 1) the render kernel writes them itself;
+ *           with any other pair a second pass on hip_stream converts them.
+ * The process-wide camera (pt_v4_set_camera / pt_v4_get_camera) is neither read nor changed, and the v4
+ * frame counter is not touched.  `cams` is consumed before the call returns.  Async on hip_stream; a
+ * plain launch (it ends a live chain, like every launch that is not a continuing chained one); there is
+ * no chained or counting form.  The views run the per-tile pool kernel's generic instances over one
+ * tile queue of nviews x tiles entries, tiles = ceil(width / 8) x ceil(nrows / 8), in view order.
+ * Checked before any GPU work -- PT_EINVAL: an invalid job (as pt_v4_render_device), cams NULL, nviews
+ * outside [1, PT_V4_MAX_VIEWS], a camera that pt_v4_set_camera would reject (pt_last_error names the
+ * view's index), pixels with an unknown format, or nviews x tiles > 2^30 - 1 (0x3fffffff, the tile
+ * index a queue entry carries: 1024 views of up to 1 048 575 tiles each, e.g. 8192 x 8184 pixels).
+ * nframes == 0 (or nrows == 0) renders nothing and returns PT_OK. */
+#define PT_V4_MAX_VIEWS 1024
+int pt_v4_render_device_views(const pt_device_job* job, const pt_v4_camera* cams, int32_t nviews, uint32_t* pixels,
+                              int32_t format, void* hip_stream);
 int pt_v4_count_device(const pt_device_job* job, void* hip_stream, pt_work_counts* out);   /* sync */
 
 /* --- tile work queue: the host tile scheduler, on the GPU ------------------------
