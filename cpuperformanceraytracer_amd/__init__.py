@@ -55,6 +55,7 @@ from .renderer import (  # noqa: F401
     v4_camera,
     v4_get_camera,
     v4_sky_window,
+    v4_get_scene_desc,
     WriteImage,
 )
 
@@ -66,5 +67,5 @@ __all__ = [
     "ClearScene", "AddMaterialToScene", "AddQuadObjectToScene", "AddSphereObjectToScene", "LoadCubemapTexture",
     "v4_config", "v4_begin_frame", "v4_get_frame", "v4_set_frame", "MakeWorkQueue", "AddWorkQueueEntry",
     "CompleteAllWork", "WorkQueue", "initialized_device", "initialized_devices", "unpin_host", "release_buffer",
-    "v4_get_config", "v4_camera", "v4_get_camera", "v4_sky_window",
+    "v4_get_config", "v4_camera", "v4_get_camera", "v4_sky_window", "v4_get_scene_desc",
 ]

@@ -45,7 +45,7 @@ EXPORTED_SYMBOLS = (
     "pt_v4_reinitialize_render_tile_data", "pt_v4_initialize_scene", "pt_v4_clear_scene", "pt_v4_add_material",
     "pt_v4_add_quad", "pt_v4_add_sphere", "pt_v4_set_frame", "pt_v4_get_frame", "pt_v4_get_scene_tables", "pt_render_opt_v4",
     "pt_copy_output_to_file", "pt_v4_render_device", "pt_v4_render_device_chain", "pt_v4_render_device_present",
-    "pt_v4_render_device_views", "pt_v4_count_device", "pt_v4_begin_frame",
+    "pt_v4_render_device_views", "pt_v4_render_device_scenes", "pt_v4_get_scene_desc", "pt_v4_count_device", "pt_v4_begin_frame",
     "pt_v4_default_camera", "pt_v4_set_camera", "pt_v4_get_camera", "pt_v4_get_sky_window",
     "pt_make_work_queue", "pt_add_work_queue_entry", "pt_complete_all_work", "pt_complete_all_work_async",
     "pt_wait_work", "pt_work_queue_size", "pt_free_work_queue",
@@ -117,6 +117,13 @@ class PtV4Material(ctypes.Structure):
 
 class PtV4Camera(ctypes.Structure):
     _fields_ = [("position", ctypes.c_float * 3), ("fov_degrees", ctypes.c_float)]
+
+
+class PtV4SceneDesc(ctypes.Structure):
+    """pt_v4_scene_desc: the reference's Add*ToScene calls as data (material i shades object i, quads first)."""
+    _fields_ = [("nquads", ctypes.c_int32), ("nspheres", ctypes.c_int32), ("nmaterials", ctypes.c_int32),
+                ("quads", (ctypes.c_float * 12) * PT_V4_MAX_OBJECTS), ("spheres", (ctypes.c_float * 4) * PT_V4_MAX_OBJECTS),
+                ("materials", PtV4Material * PT_V4_MAX_OBJECTS)]
 
 
 class PtError(RuntimeError):
@@ -205,6 +212,9 @@ def load() -> ctypes.CDLL:
         "pt_v4_render_device_chain": (i32, [ctypes.POINTER(PtDeviceJob), vp]),
         "pt_v4_render_device_present": (i32, [ctypes.POINTER(PtDeviceJob), vp, i32, vp]),
         "pt_v4_render_device_views": (i32, [ctypes.POINTER(PtDeviceJob), ctypes.POINTER(PtV4Camera), i32, vp, i32, vp]),
+        "pt_v4_render_device_scenes": (i32, [ctypes.POINTER(PtDeviceJob), ctypes.POINTER(PtV4SceneDesc), i32,
+                                             ctypes.POINTER(PtV4Camera), ctypes.POINTER(i32), i32, vp, i32, vp]),
+        "pt_v4_get_scene_desc": (i32, [ctypes.POINTER(PtV4SceneDesc)]),
         "pt_v4_count_device": (i32, [ctypes.POINTER(PtDeviceJob), vp, ctypes.POINTER(PtWorkCounts)]),
         "pt_v4_begin_frame": (i32, []),
         "pt_v4_default_camera": (None, [ctypes.POINTER(PtV4Camera)]),

@@ -148,6 +148,18 @@ struct Dev {
         bool pending = false;           // done has been recorded
     } views[kViewRing];
     unsigned views_next = 0;
+    // scenes launches (pt_v4_render_device_scenes): the same ring rule for one block per slot that holds
+    // the launch's scene records, its view table and its view -> scene mapping, in that order.  A block
+    // has the size its largest launch so far needed (a record is ~2 KiB: 1024 of them ~2 MiB), grown
+    // only after the slot's event completed.
+    struct SceneSlot {
+        unsigned char* host = nullptr;  // page-locked
+        unsigned char* dev = nullptr;
+        size_t cap = 0;                 // bytes of each
+        hipEvent_t done = nullptr;
+        bool pending = false;
+    } scenes[kViewRing];
+    unsigned scenes_next = 0;
     // chained launches (pt_render_device_chain, launch_chain): consecutive launches of one geometry
     // alternate on two streams of the library's and overlap on the GPU
     struct Chain {
@@ -388,6 +400,7 @@ const char* guard_name(uint32_t id)
         case PT_G_RECORD: return "item record slot >= 64";
         case PT_G_QUEUE_GROUP: return "queue group out of range";
         case PT_G_VIEW: return "views launch: view index beyond the view table";
+        case PT_G_SCENE: return "scenes launch: scene index beyond the scene table, or a record's object counts beyond MAX_OBJECTS";
         case PT_G_CAM_INDEX: return "camera-hit cache record outside the geometry's tiles";
         case PT_G_CAM_RECORD: return "a traced camera hit differs from its cached record; value: tile * 64 + lane";
         case PT_G_CHAIN_WAIT: return "chained launch: the previous launch's tile never became ready; value: the tile | its epoch's lag "
@@ -1464,11 +1477,16 @@ int v4_rebuild()
 
 // The sky window of the current (scene, camera) (pt_v4_skywin.h): host arithmetic, built on first use
 // after a scene edit or a camera change.  PT_MI355_V4_SKYWIN=0: no window (A/B timing, tests).
-void v4_sky_window_of(const float position[3], PtV4SkyWin* out)   // the current scene seen from `position`
+void v4_sky_window_for(const PtV4SceneDesc& d, const float position[3], PtV4SkyWin* out)   // scene `d` seen from `position`
 {
     static const bool off = getenv("PT_MI355_V4_SKYWIN") && !strcmp(getenv("PT_MI355_V4_SKYWIN"), "0");
     if (off) *out = PtV4SkyWin{-1, {}};
-    else pt_v4_skywin_build(g.v4desc.nquads, g.v4desc.quad, g.v4desc.nspheres, g.v4desc.sphere, position, out);
+    else pt_v4_skywin_build(d.nquads, d.quad, d.nspheres, d.sphere, position, out);
+}
+
+void v4_sky_window_of(const float position[3], PtV4SkyWin* out)   // the current scene seen from `position`
+{
+    v4_sky_window_for(g.v4desc, position, out);
 }
 
 const PtV4SkyWin& v4_sky_window()
@@ -1599,6 +1617,12 @@ void free_dev(Dev& dv)
         if (v.done) (void)hipEventDestroy(v.done);
         if (v.dev) (void)hipFree(v.dev);
         if (v.host) (void)hipHostFree(v.host);
+    }
+    for (Dev::SceneSlot& s : dv.scenes) {
+        if (s.pending) (void)hipEventSynchronize(s.done);
+        if (s.done) (void)hipEventDestroy(s.done);
+        if (s.dev) (void)hipFree(s.dev);
+        if (s.host) (void)hipHostFree(s.host);
     }
     for (Sched& sc : dv.sched)
         if (sc.used) free_sched(sc);
@@ -2650,6 +2674,166 @@ int pt_v4_render_device_views(const pt_device_job* dj, const pt_v4_camera* cams,
     if (e != hipSuccess) return fail(PT_EHIP, "v4 views launch failed: %s", hipGetErrorString(e));
     HIP_TRY(hipEventRecord(vs.done, st));
     vs.pending = true;
+    if ((rc = queue_done(dv, ls.slot, st, true))) return rc;
+    if (pixels && !fused) {
+        // (the slices lie back to back: one image of nviews x nrows rows in either row layout)
+        const PtToneJob tj = tone_job(j.buf, j.ncols, j.nrows * nviews, j.layout, 0, 0, pixels, format);
+        e = pt_launch_tonemap(tj, st);
+        if (e != hipSuccess) return fail(PT_EHIP, "tonemap launch failed: %s", hipGetErrorString(e));
+    }
+    return PT_OK;
+}
+
+static_assert(sizeof(pt_v4_scene_desc) == sizeof(PtV4SceneDesc) && offsetof(pt_v4_scene_desc, quads) == offsetof(PtV4SceneDesc, quad) &&
+              offsetof(pt_v4_scene_desc, spheres) == offsetof(PtV4SceneDesc, sphere) &&
+              offsetof(pt_v4_scene_desc, materials) == offsetof(PtV4SceneDesc, mat) &&
+              offsetof(pt_v4_scene_desc, nmaterials) == offsetof(PtV4SceneDesc, nmat),
+              "pt_v4_scene_desc is PtV4SceneDesc");
+
+int pt_v4_get_scene_desc(pt_v4_scene_desc* out)
+{
+    int rc;
+    if (!out) return fail(PT_EINVAL, "null scene description");
+    if ((rc = v4_ensure_scene())) return rc;
+    memcpy(out, &g.v4desc, sizeof(*out));
+    return PT_OK;
+}
+
+// A batch of scenes in one launch (include/pt_mi355.h; pt_v4.h PtV4Scenes): pt_v4_render_device_views with
+// the scene per view.  Everything is checked before the first HIP call; nothing of the process-wide scene,
+// camera or frame counter is read or written (the job is made from the arguments and the pt_v4_config
+// alone).  Each record is pt_v4_build_scene of its description -- the code behind pt_v4_add_* -- and each
+// view's window pt_v4_skywin_build of (its scene, its camera).  Records, view table and mapping travel in
+// one block of the device's scene ring (Dev::scenes).
+int pt_v4_render_device_scenes(const pt_device_job* dj, const pt_v4_scene_desc* scenes, int32_t nscenes, const pt_v4_camera* cams,
+                               const int32_t* scene_of_view, int32_t nviews, uint32_t* pixels, int32_t format, void* stream)
+{
+    int rc;
+    if (!dj) return fail(PT_EINVAL, "null device job");
+    {
+        pt_device_job geo = *dj;   // (the geometry / frame checks, as v4_device_job's)
+        geo.use_env = 0;
+        PtJob unused;
+        if ((rc = device_job(&geo, &unused))) return rc;
+    }
+    if (!cams) return fail(PT_EINVAL, "null camera array");
+    if (nviews < 1 || nviews > PT_V4_MAX_VIEWS) return fail(PT_EINVAL, "nviews %d outside [1, %d]", nviews, PT_V4_MAX_VIEWS);
+    if (pixels && format != PT_PIXEL_RGBA8 && format != PT_PIXEL_XRGB8) return fail(PT_EINVAL, "unknown pixel format %d", format);
+    const uint64_t view_tiles = (uint64_t)((dj->width + 7) / 8) * (uint64_t)((dj->nrows + 7) / 8);
+    if (view_tiles * (uint64_t)nviews > PT_TILE_MASK)
+        return fail(PT_EINVAL, "%d views x %llu tiles exceed the tile queue's %u entries", nviews, (unsigned long long)view_tiles,
+                    PT_TILE_MASK);
+    std::vector<float> dist((size_t)nviews);
+    for (int32_t v = 0; v < nviews; ++v)
+        if ((rc = v4_check_camera(&cams[v], &dist[(size_t)v], v))) return rc;
+    if (!scenes) return fail(PT_EINVAL, "null scene array");
+    if (nscenes < 1 || nscenes > PT_V4_MAX_VIEWS) return fail(PT_EINVAL, "nscenes %d outside [1, %d]", nscenes, PT_V4_MAX_VIEWS);
+    if (!scene_of_view && nscenes != nviews)
+        return fail(PT_EINVAL, "no scene_of_view: view v uses scene v, but nscenes %d != nviews %d", nscenes, nviews);
+    if (scene_of_view)
+        for (int32_t v = 0; v < nviews; ++v)
+            if (scene_of_view[v] < 0 || scene_of_view[v] >= nscenes)
+                return fail(PT_EINVAL, "view %d: scene_of_view %d outside [0, %d)", v, scene_of_view[v], nscenes);
+    const PtV4SceneDesc* const desc = reinterpret_cast<const PtV4SceneDesc*>(scenes);
+    for (int32_t s = 0; s < nscenes; ++s) {
+        const PtV4SceneDesc& d = desc[s];
+        if (d.nquads < 0 || d.nspheres < 0 || d.nmat < 0 || d.nquads > PT_V4_MAX_OBJECTS || d.nspheres > PT_V4_MAX_OBJECTS ||
+            d.nquads + d.nspheres > PT_V4_MAX_OBJECTS || d.nmat > PT_V4_MAX_OBJECTS)
+            return fail(PT_EINVAL, "scene %d: %d quads + %d spheres, %d materials (each count >= 0; objects and materials <= %d)", s,
+                        d.nquads, d.nspheres, d.nmat, PT_V4_MAX_OBJECTS);
+    }
+    if (dj->nframes == 0 || dj->nrows == 0) return PT_OK;   // nothing to render
+
+    Dev* dvp = nullptr;
+    DeviceGuard guard;
+    if ((rc = ensure_init())) return rc;
+    // the job of v4_device_job without the process-wide scene and camera: the arguments and the config
+    PtV4Job j{};
+    j.buf = dj->buf;
+    j.width = dj->width;
+    j.height = dj->height;
+    j.col0 = 0;
+    j.ncols = dj->width;
+    j.row_start = dj->row_start;
+    j.row_stride = dj->row_stride;
+    j.nrows = dj->nrows;
+    j.layout = dj->layout;
+    j.frame_first = dj->frame_first;
+    j.nframes = dj->nframes;
+    j.num_bounces = dj->num_bounces;
+    j.env_mode = PT_V4_ENV_NONE;
+    j.random_jitter = g.v4cfg.random_jitter;
+    j.rejection = g.v4cfg.rejection;
+    j.accumulate = g.v4cfg.accumulate_frames;
+    j.fast_exp = g.v4cfg.fast_exp;
+    j.sky = PtV4SkyWin{-1, {}};   // (the views' records carry the cameras and the windows)
+    if (dj->use_env) {
+        if (g.v4cfg.env_mode == PT_V4_ENV_NONE) return fail(PT_ESTATE, "use_env with v4 env mode NONE");
+        if ((rc = v4_use_env(j))) return rc;
+    }
+    if ((rc = dev_of(dj->buf, &dvp)) || (rc = use_dev(*dvp))) return rc;
+    Dev& dv = *dvp;
+    hipStream_t st = (hipStream_t)stream;
+    if (j.env_mode != PT_V4_ENV_NONE) j.env = dv.denv;
+    j.err = dv.derr;
+    // the render kernel writes the pixels with the default tonemap pair; any other pair: a second pass
+    const bool fused = pixels && g.v4cfg.fast_aces && g.v4cfg.fast_gamma;
+    j.pix_xrgb = format == PT_PIXEL_XRGB8;
+
+    const auto up16 = [](size_t n) { return (n + 15u) & ~(size_t)15u; };
+    const size_t off_views = up16((size_t)nscenes * sizeof(PtV4SceneRec));
+    const size_t off_map = off_views + up16((size_t)nviews * sizeof(PtV4View));
+    const size_t need = off_map + up16((size_t)nviews * sizeof(int32_t));
+    Dev::SceneSlot& ss = dv.scenes[dv.scenes_next++ % kViewRing];
+    if (!ss.done) HIP_TRY(hipEventCreateWithFlags(&ss.done, hipEventDisableTiming));
+    if (ss.pending) {   // the slot's previous launch (kViewRing launches back) still reads the block: wait for it
+        HIP_TRY(hipEventSynchronize(ss.done));
+        ss.pending = false;
+    }
+    if (ss.cap < need) {   // (no launch reads the slot's block now)
+        if (ss.host) (void)hipHostFree(ss.host);
+        if (ss.dev) (void)hipFree(ss.dev);
+        ss.host = ss.dev = nullptr;
+        ss.cap = 0;
+        const size_t cap = (need + 4095u) & ~(size_t)4095u;
+        if (hipHostMalloc((void**)&ss.host, cap, hipHostMallocDefault) != hipSuccess) {
+            ss.host = nullptr;
+            return fail(PT_ENOMEM, "hipHostMalloc(scene table, %zu bytes) failed", cap);
+        }
+        if (hipMalloc((void**)&ss.dev, cap) != hipSuccess) {
+            (void)hipHostFree(ss.host);
+            ss.host = ss.dev = nullptr;
+            return fail(PT_ENOMEM, "hipMalloc(scene table, %zu bytes) failed", cap);
+        }
+        ss.cap = cap;
+    }
+    PtV4SceneRec* const hrec = reinterpret_cast<PtV4SceneRec*>(ss.host);
+    PtV4View* const hview = reinterpret_cast<PtV4View*>(ss.host + off_views);
+    int32_t* const hmap = reinterpret_cast<int32_t*>(ss.host + off_map);
+    for (int32_t s = 0; s < nscenes; ++s) {
+        if (pt_v4_build_scene(&desc[s], &hrec[s].sc)) return fail(PT_EINVAL, "scene %d exceeds MAX_OBJECTS", s);   // (checked above)
+        memset(hrec[s].mx, 0, sizeof(hrec[s].mx));   // (the preparation kernel fills them on the device)
+    }
+    for (int32_t v = 0; v < nviews; ++v) {
+        const int32_t s = scene_of_view ? scene_of_view[v] : v;
+        hmap[v] = s;
+        PtV4View& r = hview[v];
+        memcpy(r.cam_pos, cams[v].position, sizeof(r.cam_pos));
+        r.cam_dist = dist[(size_t)v];
+        v4_sky_window_for(desc[s], cams[v].position, &r.sky);
+    }
+    HIP_TRY(hipMemcpyAsync(ss.dev, ss.host, need, hipMemcpyHostToDevice, st));
+
+    LaunchSched ls;
+    if ((rc = chain_join(dv, st)) || (rc = use_queue_slot(dv, st, &ls))) return rc;
+    j.queue = ls.queue;
+    j.queue_next = ls.queue_next;
+    const PtV4Views va{reinterpret_cast<const PtV4View*>(ss.dev + off_views), nviews, fused ? pixels : nullptr, g.v4_views_grid};
+    const PtV4Scenes sa{reinterpret_cast<PtV4SceneRec*>(ss.dev), nscenes, reinterpret_cast<const int32_t*>(ss.dev + off_map)};
+    hipError_t e = pt_launch_v4_scenes(j, va, sa, st);
+    if (e != hipSuccess) return fail(PT_EHIP, "v4 scenes launch failed: %s", hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(ss.done, st));
+    ss.pending = true;
     if ((rc = queue_done(dv, ls.slot, st, true))) return rc;
     if (pixels && !fused) {
         // (the slices lie back to back: one image of nviews x nrows rows in either row layout)

@@ -109,6 +109,8 @@ enum PtGuardId : uint32_t {
     PT_G_CAM_INDEX = 14,    // a camera-hit cache record outside the geometry's tiles
     PT_G_CAM_RECORD = 15,   // a counted launch traced a camera hit that differs from its cached record (every build)
     PT_G_VIEW = 16,         // a views launch: a tile entry's view index beyond the view table
+    PT_G_SCENE = 17,        // a scenes launch: a view's scene index beyond the scene table, or (value | 2^31) a
+                            // scene record whose object counts exceed PT_V4_MAX_OBJECTS
 };
 
 // Tile queues: one counter per XCD group, 128 B apart (PT_QUEUE_WORDS u32 per launch).

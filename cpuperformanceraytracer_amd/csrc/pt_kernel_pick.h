@@ -263,3 +263,20 @@ constexpr PtKeyList<PtV4ViewsKey, kPtV4ViewsKeyCount> pt_v4_views_key_list()
     return l;
 }
 constexpr PtKeyList<PtV4ViewsKey, kPtV4ViewsKeyCount> kPtV4ViewsKeys = pt_v4_views_key_list();
+
+// ---- v4 scenes (pt_v4.hip pt_v4_scenes_kernel <env, layout, fexp>) ----
+// A batch of scenes runs the same generic form as a batch of views, with the scene as a per-view record:
+// the same 12 keys, in a list of its own (its instances are other kernels).
+struct PtV4ScenesKey {
+    int env, layout, fexp;
+    constexpr bool operator==(const PtV4ScenesKey& o) const { return env == o.env && layout == o.layout && fexp == o.fexp; }
+};
+constexpr PtV4ScenesKey pt_pick_v4_scenes_key(int env, int layout, bool fast_exp) { return {env, layout, fast_exp ? 1 : 0}; }
+constexpr size_t kPtV4ScenesKeyCount = kPtV4ViewsKeyCount;
+constexpr PtKeyList<PtV4ScenesKey, kPtV4ScenesKeyCount> pt_v4_scenes_key_list()
+{
+    PtKeyList<PtV4ScenesKey, kPtV4ScenesKeyCount> l{};
+    for (size_t i = 0; i < kPtV4ScenesKeyCount; ++i) l.k[i] = {kPtV4ViewsKeys.k[i].env, kPtV4ViewsKeys.k[i].layout, kPtV4ViewsKeys.k[i].fexp};
+    return l;
+}
+constexpr PtKeyList<PtV4ScenesKey, kPtV4ScenesKeyCount> kPtV4ScenesKeys = pt_v4_scenes_key_list();

@@ -145,3 +145,30 @@ struct PtV4Views {
 // The generic instances (ENV x row layout x FEXP), unscheduled (job.order, units, cost: nullptr), a
 // plain launch.  job.ncols == job.width, job.col0 == 0 (a device job).
 hipError_t pt_launch_v4_views(const PtV4Job& job, const PtV4Scene& scene, const PtV4Views& views, hipStream_t stream);
+
+// ---- a batch of scenes in one launch (pt_v4_render_device_scenes; pt_v4.hip pt_v4_scenes_kernel) ----
+// A views launch whose views each name a scene: the scene is a record of a device table instead of a
+// kernel argument.  Record s holds pt_v4_build_scene's tables of scene s and, per material, the five
+// constants of pt_v4.hip's mat_consts -- filled on the device (pt_v4_scenes_prep_kernel, on the launch's
+// stream before the render kernel), because they come from the device's rcp sequence and fresnel_m has
+// to see the bits it sees in the plain kernels.  View v's scene is scene_of_view[v] (a parallel array of
+// the view table: PtV4View and the views kernels stay as they are).  The geometry is read through the
+// constant address space (the record's address is wave-uniform), a hit's material row and constants by
+// the lane from the record in global memory: no block-wide material table exists in this kernel, so the
+// four waves of a block can be on four scenes at once.
+#define PT_V4_MATX_FLOATS 5   // pt_v4.hip MatX: r0sq, omr0, rior, nnout, rscc
+struct PtV4SceneRec {
+    PtV4Scene sc;
+    float mx[PT_V4_MAX_OBJECTS][PT_V4_MATX_FLOATS];   // written by pt_v4_scenes_prep_kernel
+};
+static_assert(sizeof(PtV4SceneRec) % 4 == 0 && sizeof(PtV4SceneRec) == sizeof(PtV4Scene) + PT_V4_MAX_OBJECTS * PT_V4_MATX_FLOATS * 4,
+              "a scene record is whole dwords, no padding");
+struct PtV4Scenes {
+    PtV4SceneRec* table;             // device memory, nscenes records (mx filled by the preparation kernel)
+    int32_t nscenes;
+    const int32_t* scene_of_view;    // device memory, one entry per view, each in [0, nscenes)
+};
+// The preparation kernel and then the render kernel on `stream`: the generic instances (ENV x row layout x
+// FEXP) of pt_v4_scenes_kernel, launched as pt_launch_v4_views launches its own (unscheduled, a plain
+// launch, views.grid_cap honoured).
+hipError_t pt_launch_v4_scenes(const PtV4Job& job, const PtV4Views& views, const PtV4Scenes& scenes, hipStream_t stream);

@@ -647,6 +647,57 @@ __device__ __forceinline__ Hit trace(const PtV4Scene& sc, V3 pos, V3 dir, const 
     return h;
 }
 
+// The scene of one view of a scenes launch (pt_v4.h PtV4Scenes): what trace<false> and v4_segment read
+// from the kernel-argument scene, read from the view's scene record instead.  take() runs when a wave
+// takes a tile, right after V4ViewCam::take -- a persistent wave crosses from one scene's tiles to
+// another's, so the record pointer, both object counts and both material pointers are replaced there
+// and nothing of the previous scene survives.  Geometry goes through the constant address space (the
+// record's address is wave-uniform: scalar loads, as the kernel-argument scene's); a hit's material row
+// and its MatX constants are per-lane loads from the record in global memory (PT_V4_SCENES_LDS 0), or
+// from this wave's own LDS rows, refilled by take() (PT_V4_SCENES_LDS 1, the A/B build: DESIGN.md 3b).
+#ifndef PT_V4_SCENES_LDS
+#define PT_V4_SCENES_LDS 0
+#endif
+static_assert(sizeof(MatX) == PT_V4_MATX_FLOATS * sizeof(float), "PtV4SceneRec::mx rows are MatX");
+struct V4SceneRec {
+    typedef const __attribute__((address_space(4))) PtV4SceneRec* Rec;
+    typedef const __attribute__((address_space(4))) float* F;
+    Rec rec = nullptr;
+    int32_t nquads = 0, nspheres = 0;
+    const PtV4Mat* mat = nullptr;   // PT_V4_MAX_OBJECTS rows, by object index
+    const MatX* mx = nullptr;       // their constants (pt_v4_scenes_prep_kernel)
+    __device__ __forceinline__ void take(const PtV4SceneRec* table, uint32_t scene)
+    {
+        rec = (Rec)(table + scene);
+        nquads = rec->sc.nquads;
+        nspheres = rec->sc.nspheres;
+        mat = table[scene].sc.mat;
+        mx = reinterpret_cast<const MatX*>(table[scene].mx);
+    }
+    static __device__ __forceinline__ V3 ld3(F p) { return v3(p[0], p[1], p[2]); }
+};
+
+// trace<false> on a scene record: the same tests in the same order on the same values
+template <bool DEF>
+__device__ __forceinline__ Hit trace(const V4SceneRec& sc, V3 pos, V3 dir, const float4*, int&)
+{
+    static_assert(!DEF, "a scene record is traced by the generic form");
+    Hit h{kSuperFar, v3(0.0f, 0.0f, 0.0f), false, 0};
+    int obj = 0;
+    for (int i = 0; i < sc.nquads; ++i, ++obj) {
+        const V4SceneRec::F t = &sc.rec->sc.quad[i].v0[0];   // v0, n, a0, a1, b0, b1: 18 f32 (PtV4Quad)
+        const auto dk = [t](V3 v, int, int k) { return dot(v, V4SceneRec::ld3(t + 3 * k)); };
+        quad_test<false>(pos, dir, h, obj, V4SceneRec::ld3(t), V4SceneRec::ld3(t + 3), dk, i);
+    }
+    for (int i = 0; i < sc.nspheres; ++i, ++obj) {
+        const V4SceneRec::F s = &sc.rec->sc.sph[i][0];
+        sphere_test(pos, dir, h, obj, V4SceneRec::ld3(s), s[3]);
+    }
+    return h;
+}
+static_assert(sizeof(PtV4Quad) == 18 * sizeof(float) && offsetof(PtV4Quad, n) == 12 && offsetof(PtV4Quad, a0) == 24,
+              "quad rows are read as 6 vectors from v0");
+
 template <int LAYOUT>
 __device__ __forceinline__ size_t out_index(const PtV4Job& j, int x, int r)   // r = buffer row
 {
@@ -670,8 +721,9 @@ __device__ __forceinline__ size_t pixel_extent(const PtV4Job& j)
 
 // One iteration of an item's path: GetColorForRay's bounce loop, :733-909 (the pool kernels' shared
 // body).  done: the path ended (queued: DEFER, the miss's env term is deferred to the queue's drain).
-template <int ENV, bool COUNT, bool DEF, int FEXP, bool DFL>
-__device__ __forceinline__ void v4_segment(const PtV4Job& job, const PtV4Scene& sc, const PtV4Mat* s_mat,
+// SC: the kernel-argument scene (PtV4Scene) or a view's scene record (V4SceneRec, with s_mat / s_mx its rows).
+template <int ENV, bool COUNT, bool DEF, int FEXP, bool DFL, class SC>
+__device__ __forceinline__ void v4_segment(const PtV4Job& job, const SC& sc, const PtV4Mat* s_mat,
                                            const MatX* s_mx, const float4* s_sc, const Tex& tex, bool random,
                                            bool rejection, int B, bool all_sky, V3& pos, V3& dir, V3& T, V3& ret,
                                            uint32_t& rng, int& bounce, bool& done, bool& queued,
@@ -880,8 +932,10 @@ __device__ __forceinline__ void v4_present(const PtV4Job& job, int X, int Y, V3 
 template <int ENV, int LAYOUT, bool COUNT, bool DEF, int FEXP, bool DFL = false, bool PRESENT = false>
 __global__ __launch_bounds__(64 * kWaves) PT_V4_OCC void pt_v4_kernel(PtV4Job job, PtV4Scene sc)
 {
-    constexpr bool VIEWS = false;
+    constexpr bool VIEWS = false, SCENES = false;
     constexpr PtV4Views va{nullptr, 0, nullptr, 0u};   // (named in discarded statements only)
+    constexpr PtV4Scenes sa{nullptr, 0, nullptr};      // (likewise)
+    V4SceneRec srec;                                   // (likewise)
     const V4Cam<DEF> cam(job);   // camera.Distance, camera.Position (InitializeCamera :1500-1501)
 #include "pt_v4_tile_pool.inc"
 }
@@ -894,9 +948,44 @@ template <int ENV, int LAYOUT, int FEXP>
 __global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_views_kernel(PtV4Job job, PtV4Scene sc, PtV4Views va)
 {
     static_assert(LAYOUT != PT_LAYOUT_TILED_PLANAR8, "views run the generic, uncounted row-layout form");
-    constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false;
+    constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = false;
+    constexpr PtV4Scenes sa{nullptr, 0, nullptr};   // (named in discarded statements only)
+    V4SceneRec srec;                                // (likewise)
     V4ViewCam cam;   // the tile's view's camera (take(), when the wave takes a tile)
 #include "pt_v4_tile_pool.inc"
+}
+
+// A batch of scenes in one launch (pt_v4_render_device_scenes, pt_v4.h PtV4Scenes): the views kernel with
+// the scene as a record of the view (V4SceneRec) instead of a kernel argument -- the same 12 instances
+// (pt_kernel_pick.h kPtV4ScenesKeys).  Everything it adds to the pool's body sits under `if constexpr
+// (SCENES)`.  No block-wide material table: the four waves of a block may be on four scenes at once.
+template <int ENV, int LAYOUT, int FEXP>
+__global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_scenes_kernel(PtV4Job job, PtV4Views va, PtV4Scenes sa)
+{
+    static_assert(LAYOUT != PT_LAYOUT_TILED_PLANAR8, "scenes run the generic, uncounted row-layout form");
+    constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = true;
+    constexpr PtV4Scene sc{};   // (named in discarded statements only)
+    V4ViewCam cam;      // the tile's view's camera
+    V4SceneRec srec;    // and its scene (both taken when the wave takes a tile)
+#include "pt_v4_tile_pool.inc"
+}
+
+// The per-material constants of every record of a scenes launch's table (PtV4SceneRec::mx): mat_consts
+// itself, on the device, one thread per (scene, material row) -- all PT_V4_MAX_OBJECTS rows, as the plain
+// kernels' blocks evaluate them.
+__global__ __launch_bounds__(256) void pt_v4_scenes_prep_kernel(PtV4SceneRec* table, int32_t nscenes)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= (uint32_t)nscenes * PT_V4_MAX_OBJECTS) return;
+    PtV4SceneRec& r = table[t / PT_V4_MAX_OBJECTS];
+    const uint32_t m = t % PT_V4_MAX_OBJECTS;
+    const MatX x = mat_consts(r.sc.mat[m]);
+    float* const o = r.mx[m];
+    o[0] = x.r0sq;
+    o[1] = x.omr0;
+    o[2] = x.rior;
+    o[3] = x.nnout;
+    o[4] = x.rscc;
 }
 
 // ---- continuous tiles (CT): the v4 pool without per-tile tails ----------------------------------
@@ -1409,6 +1498,21 @@ constexpr PtKeyList<V4ViewsInstance, sizeof...(I)> v4_views_table(std::index_seq
 constexpr auto kV4ViewsTable = v4_views_table(std::make_index_sequence<kPtV4ViewsKeyCount>{});
 PtResidentCache<kPtV4ViewsKeyCount> v4_views_resident;
 
+// The scenes instances: entry i is the kernel of kPtV4ScenesKeys[i], as above.
+using V4ScenesKernel = void (*)(PtV4Job, PtV4Views, PtV4Scenes);
+struct V4ScenesInstance {
+    PtV4ScenesKey key;
+    V4ScenesKernel kern;
+};
+template <size_t... I>
+constexpr PtKeyList<V4ScenesInstance, sizeof...(I)> v4_scenes_table(std::index_sequence<I...>)
+{
+    constexpr auto& k = kPtV4ScenesKeys.k;
+    return {{V4ScenesInstance{k[I], pt_v4_scenes_kernel<k[I].env, k[I].layout, k[I].fexp>}...}};
+}
+constexpr auto kV4ScenesTable = v4_scenes_table(std::make_index_sequence<kPtV4ScenesKeyCount>{});
+PtResidentCache<kPtV4ScenesKeyCount> v4_scenes_resident;
+
 }  // namespace
 
 hipError_t pt_v4_set_chain_polls(uint32_t polls)
@@ -1475,5 +1579,29 @@ hipError_t pt_launch_v4_views(const PtV4Job& j, const PtV4Scene& sc, const PtV4V
     uint32_t grid = pt_pick_grid((uint32_t)r, (uint32_t)tiles, kWaves);
     if (va.grid_cap && grid > va.grid_cap) grid = va.grid_cap;
     hipLaunchKernelGGL(kV4ViewsTable.k[i].kern, dim3(grid), dim3(64 * kWaves), 0, st, j, sc, va);
+    return hipGetLastError();
+}
+
+hipError_t pt_launch_v4_scenes(const PtV4Job& j, const PtV4Views& va, const PtV4Scenes& sa, hipStream_t st)
+{
+    if (j.ncols <= 0 || j.nrows <= 0 || j.nframes <= 0) return hipSuccess;
+    if (!va.table || va.nviews < 1 || j.col0 != 0 || j.ncols != j.width) return hipErrorInvalidValue;
+    if (!sa.table || sa.nscenes < 1 || !sa.scene_of_view) return hipErrorInvalidValue;
+    if (j.env_mode != PT_V4_ENV_NONE_ && (!j.env || j.env_w <= 0 || j.env_h <= 0)) return hipErrorInvalidValue;
+    if (!j.queue || j.order || j.units || j.cost || j.counters) return hipErrorInvalidValue;   // unscheduled, uncounted
+    if (!pt_pick_v4_views_valid(j.env_mode, j.layout)) return hipErrorInvalidValue;
+    const uint64_t tiles = (uint64_t)((j.ncols + 7) / 8) * (uint64_t)((j.nrows + 7) / 8) * (uint64_t)va.nviews;
+    if (tiles > PT_TILE_MASK) return hipErrorInvalidValue;   // (a queue entry carries view * tiles + tile)
+    const int i = kPtV4ScenesKeys.find(pt_pick_v4_scenes_key(j.env_mode, j.layout, j.fast_exp != 0));
+    const int r = i < 0 ? 0 : v4_scenes_resident.get((size_t)i, (const void*)kV4ScenesTable.k[i].kern, 64 * kWaves);
+    if (r <= 0) return i < 0 ? hipErrorInvalidValue : hipErrorInvalidDevice;
+    uint32_t grid = pt_pick_grid((uint32_t)r, (uint32_t)tiles, kWaves);
+    if (va.grid_cap && grid > va.grid_cap) grid = va.grid_cap;
+    // the records' material constants first (same stream: the render kernel starts after it)
+    const uint32_t rows = (uint32_t)sa.nscenes * PT_V4_MAX_OBJECTS;
+    hipLaunchKernelGGL(pt_v4_scenes_prep_kernel, dim3((rows + 255u) / 256u), dim3(256), 0, st, sa.table, sa.nscenes);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kV4ScenesTable.k[i].kern, dim3(grid), dim3(64 * kWaves), 0, st, j, va, sa);
     return hipGetLastError();
 }

@@ -1,17 +1,26 @@
 // pt_v4_tile_pool.inc -- the body of the v4 per-tile pool kernels (pt_v4.hip includes it inside
-// pt_v4_kernel and pt_v4_views_kernel, which declare ENV, LAYOUT, COUNT, DEF, FEXP, DFL, PRESENT, VIEWS,
-// the kernel arguments job and sc, `cam` and the views arguments `va`).
+// pt_v4_kernel, pt_v4_views_kernel and pt_v4_scenes_kernel, which declare ENV, LAYOUT, COUNT, DEF, FEXP,
+// DFL, PRESENT, VIEWS, SCENES, the kernel arguments job and sc, `cam`, the views arguments `va`, the scenes
+// arguments `sa` and the view's scene `srec`).
+    // SCENES: no block-wide material table (each wave follows its own view's scene: srec.mat / srec.mx).
+    // SLDS (the A/B build PT_V4_SCENES_LDS=1): a table per wave in LDS, refilled when the wave takes a tile,
+    // paid for by a shorter env miss queue, so that the block stays within 25 LDS granules.
+    constexpr bool SLDS = SCENES && PT_V4_SCENES_LDS != 0;
+    constexpr int kQ = SLDS ? 24 : kEnvQ;   // entries of the env miss queue
+    constexpr int kMatRows = SCENES ? (SLDS ? kWaves * PT_V4_MAX_OBJECTS : 1) : PT_V4_MAX_OBJECTS;
     __shared__ float s_col[kWaves][kChunk * 64 * 3];
-    __shared__ PtV4Mat s_mat[PT_V4_MAX_OBJECTS];
+    __shared__ PtV4Mat s_mat[kMatRows];
     __shared__ float4 s_sc[DEF ? pt_v4_default::kSpheres : 1];   // default scene: sphere centre, radius
-    __shared__ MatX s_mx[PT_V4_MAX_OBJECTS];                        // per-material constants (mat_consts)
+    __shared__ MatX s_mx[kMatRows];                                 // per-material constants (mat_consts)
     constexpr bool DEFER = ENV != PT_V4_ENV_NONE_;
-    __shared__ float4 s_qd[DEFER ? kWaves : 1][DEFER ? kEnvQ : 1];   // env dir, rng
-    __shared__ float4 s_qt[DEFER ? kWaves : 1][DEFER ? kEnvQ : 1];   // throughput, colour slot
+    __shared__ float4 s_qd[DEFER ? kWaves : 1][DEFER ? kQ : 1];   // env dir, rng
+    __shared__ float4 s_qt[DEFER ? kWaves : 1][DEFER ? kQ : 1];   // throughput, colour slot
+    if constexpr (!SCENES) {
     for (int t = threadIdx.x; t < PT_V4_MAX_OBJECTS * 17; t += 64 * kWaves)
         reinterpret_cast<float*>(s_mat)[t] = reinterpret_cast<const float*>(sc.mat)[t];
     __syncthreads();
     if (threadIdx.x < PT_V4_MAX_OBJECTS) s_mx[threadIdx.x] = mat_consts(s_mat[threadIdx.x]);
+    }
     if (DEF && threadIdx.x < pt_v4_default::kSpheres) {
         const float* c = pt_v4_default::kSphere[threadIdx.x];
         s_sc[threadIdx.x] = make_float4(c[0], c[1], c[2], c[3]);
@@ -52,6 +61,32 @@
         if (!PT_GUARD(job.err, view < (uint32_t)va.nviews, PT_G_VIEW, view)) view = 0;   // (checked build: reported)
         cam.take(va.table, view);
         if (!PT_GUARD(job.err, cam.nrects <= PT_V4_SKYWIN_MAX, PT_G_VIEW, 0x80000000u | view)) cam.nrects = -1;
+    }
+    if constexpr (SCENES) {
+        // and so is the scene: the record pointer, both object counts and the material pointers are
+        // replaced (a scene with fewer objects, or none, after one with more; equal geometry with other
+        // materials).  The index comes from the view's entry of the mapping, a scalar load like the record's.
+        uint32_t scene = (uint32_t)((const __attribute__((address_space(4))) int32_t*)sa.scene_of_view)[view];
+        if (!PT_GUARD(job.err, scene < (uint32_t)sa.nscenes, PT_G_SCENE, scene)) scene = 0;   // (checked build: reported)
+        srec.take(sa.table, scene);
+        if (!PT_GUARD(job.err, srec.nquads >= 0 && srec.nspheres >= 0 && srec.nquads + srec.nspheres <= PT_V4_MAX_OBJECTS,
+                      PT_G_SCENE, 0x80000000u | scene))
+            srec.nquads = srec.nspheres = 0;
+        if constexpr (SLDS) {
+            // this wave's rows only, written and read by this wave alone: its reads of the previous tile's
+            // rows are done (program order), the refill is fenced like s_col's
+            float* const wm = reinterpret_cast<float*>(s_mat + wv * PT_V4_MAX_OBJECTS);
+            float* const wx = reinterpret_cast<float*>(s_mx + wv * PT_V4_MAX_OBJECTS);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            for (int t = lane; t < PT_V4_MAX_OBJECTS * 17; t += 64) wm[t] = reinterpret_cast<const float*>(srec.mat)[t];
+            if (lane < PT_V4_MAX_OBJECTS * PT_V4_MATX_FLOATS) wx[lane] = reinterpret_cast<const float*>(srec.mx)[lane];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            srec.mat = s_mat + wv * PT_V4_MAX_OBJECTS;
+            srec.mx = s_mx + wv * PT_V4_MAX_OBJECTS;
+        }
     }
     const int tcol = (vtile % tiles_x) * 8, trow = (vtile / tiles_x) * 8;
     uint32_t tile_work = 1;   // pool iterations of this tile (the schedule's cost)
@@ -149,6 +184,10 @@
                 all_sky = pt_ballot(item >= 0 && !cam.sky(dir)) == 0;
             if (item >= 0) {
                 bool done = false;
+                if constexpr (SCENES)   // the view's scene record and its material rows
+                    v4_segment<ENV, COUNT, DEF, FEXP, DFL>(job, srec, srec.mat, srec.mx, s_sc, tex, random, rejection, B, all_sky,
+                                                           pos, dir, T, ret, rng, bounce, done, queued, n_seg, n_esc, n_fb, n_sky);
+                else
                 v4_segment<ENV, COUNT, DEF, FEXP, DFL>(job, sc, s_mat, s_mx, s_sc, tex, random, rejection, B, all_sky, pos,
                                                        dir, T, ret, rng, bounce, done, queued, n_seg, n_esc, n_fb, n_sky);
                 if (done) {
@@ -172,7 +211,7 @@
                 const unsigned long long qm = pt_ballot(queued);
                 const int nq = __builtin_popcountll(qm);
                 const V3 ed = ENV == PT_V4_ENV_EQUIRECT_ ? v3(-dir.x, dir.y, -dir.z) : dir;
-                if (qn + nq > kEnvQ) {
+                if (qn + nq > kQ) {
                     // overflow: one env pass over the whole wave -- the new misses in their own lanes,
                     // the other lanes each take one queued miss (the top `take` entries, so the rest
                     // stay in place).  At least kEnvQ + 1 lanes busy (min(qn + nq, 64)); the drain-or-

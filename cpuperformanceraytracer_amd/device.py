@@ -255,6 +255,74 @@ def render_v4_device_views(buf, cameras, width: int, height: int, *, frame_first
                                                pixel_format, _stream(stream)), "pt_v4_render_device_views")
 
 
+def v4_scene_desc(scene) -> "N.PtV4SceneDesc":
+    """A pt_v4_scene_desc from {"quads", "spheres", "materials"} (or a (quads, spheres, materials) sequence):
+    quads 4 x 3 (V0..V3), spheres (x, y, z, r), materials dicts with the keys of renderer.v4_get_scene_desc
+    (or AddMaterialToScene's long names; missing fields are zero, like `SceneMaterial{ 0 }`).  The counts are
+    passed on as given -- the library rejects a scene that is too large -- but only what fits is copied."""
+    import numpy as np
+    from .renderer import _MAT_KEYS
+    if isinstance(scene, N.PtV4SceneDesc):
+        return scene
+    if isinstance(scene, dict):
+        quads, spheres, mats = scene.get("quads", ()), scene.get("spheres", ()), scene.get("materials", ())
+    else:
+        quads, spheres, mats = scene
+    d = N.PtV4SceneDesc()
+    d.nquads, d.nspheres, d.nmaterials = len(quads), len(spheres), len(mats)
+    for i, q in enumerate(quads[:N.PT_V4_MAX_OBJECTS]):
+        d.quads[i][:] = [float(x) for x in np.asarray(q, np.float32).reshape(12)]
+    for i, p in enumerate(spheres[:N.PT_V4_MAX_OBJECTS]):
+        d.spheres[i][:] = [float(x) for x in np.asarray(p, np.float32).reshape(4)]
+    for i, m in enumerate(mats[:N.PT_V4_MAX_OBJECTS]):
+        for short, long in _MAT_KEYS:
+            v = m.get(short, m.get(long))
+            if v is None:
+                continue
+            if short in ("albedo", "emissive", "spec_color", "refr_color"):
+                getattr(d.materials[i], long)[:] = [float(x) for x in v]
+            else:
+                setattr(d.materials[i], long, float(v))
+    return d
+
+
+def render_v4_device_scenes(buf, scenes, cameras, width: int, height: int, scene_of_view=None, *, frame_first: int,
+                            nframes: int, num_bounces: int = 8, row_start: int = 0, row_stride: int = 1,
+                            nrows: int | None = None, layout: int = N.PT_LAYOUT_INTERLEAVED, use_env: bool = False,
+                            pixels=None, pixel_format: int = N.PT_PIXEL_RGBA8, stream=None) -> None:
+    """A batch of scenes in one launch (pt_v4_render_device_scenes): render_v4_device_views with a scene per
+    view.  `scenes` is a sequence of scene descriptions (v4_scene_desc), `cameras` one (position,
+    fov_degrees) per view; view v renders scenes[scene_of_view[v]] -- scene v when scene_of_view is None,
+    which needs as many scenes as cameras.  Slice v of `buf` ends bit for bit as ClearScene, the
+    description's Add*ToScene calls, v4_camera(*cameras[v]) and render_v4_device on it would leave it; the
+    scene of Add*ToScene, the camera of v4_camera and the v4 frame counter are neither read nor changed.
+    Asynchronous on `stream`."""
+    nrows = height if nrows is None else nrows
+    cams = [(tuple(float(x) for x in pos), float(fov)) for pos, fov in cameras]
+    nviews = len(cams)
+    if any(len(pos) != 3 for pos, _ in cams):
+        raise N.PtError(N.PT_EINVAL, "render_v4_device_scenes", "a camera position has three components")
+    if not 1 <= nviews <= N.PT_V4_MAX_VIEWS:
+        raise N.PtError(N.PT_EINVAL, "render_v4_device_scenes", f"{nviews} cameras outside [1, {N.PT_V4_MAX_VIEWS}]")
+    descs = [v4_scene_desc(s) for s in scenes]
+    if not descs:
+        raise N.PtError(N.PT_EINVAL, "render_v4_device_scenes", "no scenes")
+    job = _job(buf, width, height, row_start, row_stride, nviews * nrows, frame_first, nframes, num_bounces, layout, use_env)
+    job.nrows = nrows
+    if pixels is not None:
+        _check_pixels(pixels, nviews * nrows * width, buf)
+    arr = (N.PtV4Camera * nviews)(*[N.PtV4Camera((ctypes.c_float * 3)(*pos), fov) for pos, fov in cams])
+    sarr = (N.PtV4SceneDesc * len(descs))(*descs)
+    smap = None
+    if scene_of_view is not None:
+        if len(scene_of_view) != nviews:
+            raise N.PtError(N.PT_EINVAL, "render_v4_device_scenes", f"scene_of_view has {len(scene_of_view)} entries for {nviews} views")
+        smap = (ctypes.c_int32 * nviews)(*[int(s) for s in scene_of_view])
+    N.check(N.load().pt_v4_render_device_scenes(ctypes.byref(job), sarr, len(descs), arr, smap, nviews,
+                                                pixels.data_ptr() if pixels is not None else None, pixel_format,
+                                                _stream(stream)), "pt_v4_render_device_scenes")
+
+
 def count_v4_device(buf, width: int, height: int, *, frame_first: int, nframes: int, num_bounces: int = 8,
                     row_start: int = 0, row_stride: int = 1, nrows: int | None = None,
                     layout: int = N.PT_LAYOUT_INTERLEAVED, use_env: bool = False, stream=None) -> dict:

@@ -488,6 +488,28 @@ def v4_scene_tables() -> tuple[np.ndarray, int, int]:
     return out, nq.value, ns.value
 
 
+_MAT_KEYS = (("albedo", "albedo"), ("emissive", "emissive"), ("spec_chance", "specular_chance"),
+             ("spec_rough", "specular_roughness"), ("spec_color", "specular_color"), ("ior", "ior"),
+             ("refr_chance", "refraction_chance"), ("refr_rough", "refraction_roughness"),
+             ("refr_color", "refraction_color"))
+
+
+def v4_get_scene_desc() -> dict:
+    """The current v4 scene as a description (pt_v4_get_scene_desc): {"quads": [4 x 3 arrays], "spheres":
+    [(x, y, z, r) arrays], "materials": [dicts: albedo, emissive, spec_chance, spec_rough, spec_color, ior,
+    refr_chance, refr_rough, refr_color]} -- what Add*ToScene was given (InitializeScene's calls for the
+    default scene), the shape device.render_v4_device_scenes takes.  Host only."""
+    d = N.PtV4SceneDesc()
+    N.check(N.load().pt_v4_get_scene_desc(ctypes.byref(d)), "pt_v4_get_scene_desc")
+    mats = []
+    for i in range(d.nmaterials):
+        m = d.materials[i]
+        mats.append({short: (tuple(float(x) for x in getattr(m, long)) if short in ("albedo", "emissive", "spec_color", "refr_color")
+                             else float(getattr(m, long))) for short, long in _MAT_KEYS})
+    return {"quads": [np.array(d.quads[i], np.float32).reshape(4, 3) for i in range(d.nquads)],
+            "spheres": [np.array(d.spheres[i], np.float32) for i in range(d.nspheres)], "materials": mats}
+
+
 def v4_camera(position=(0.0, 0.0, 40.0), fov_degrees: float = 90.0) -> None:
     """The v4 camera (camera.Position, c_FOVDegrees: v4 :1501, :20) for every v4 entry point; the view
     direction stays -z with no roll, as the reference's.  Host state only: the frame counter and the

@@ -362,6 +362,37 @@ int pt_v4_render_device_present(const pt_device_job* job, uint32_t* pixels, int3
 #define PT_V4_MAX_VIEWS 1024
 int pt_v4_render_device_views(const pt_device_job* job, const pt_v4_camera* cams, int32_t nviews, uint32_t* pixels,
                               int32_t format, void* hip_stream);
+/* A scene as data: the reference's Add*ToScene calls written down (material i shades object i, quads
+ * first).  pt_v4_get_scene_desc returns the current scene's description -- InitializeScene's, or the
+ * edited one -- so a caller can start from the default scene and change one field (host only, no GPU). */
+typedef struct pt_v4_scene_desc {
+    int32_t nquads, nspheres, nmaterials;
+    float quads[PT_V4_MAX_OBJECTS][12];          /* V0..V3 xyz, AddQuadObjectToScene order    */
+    float spheres[PT_V4_MAX_OBJECTS][4];         /* PositionAndRadius, AddSphereObjectToScene */
+    pt_v4_material materials[PT_V4_MAX_OBJECTS]; /* as passed to AddMaterialToScene           */
+} pt_v4_scene_desc;
+int pt_v4_get_scene_desc(pt_v4_scene_desc* out);
+/* A batch of SCENES in one launch: pt_v4_render_device_views with a scene per view.  View v renders
+ * scenes[scene_of_view[v]] seen by cams[v]; scene_of_view == NULL means view v uses scene v and requires
+ * nscenes == nviews.  One scene can take many cameras (a turntable is nscenes == 1) and many scenes can
+ * share a camera: animations, material sweeps, a random scene per sample of a dataset.
+ *   job, pixels, format, hip_stream: as pt_v4_render_device_views (the same slices, limits, asynchrony
+ *           and nframes == 0 / nrows == 0 shortcut).
+ *   result  view v's slice is bit for bit what pt_v4_clear_scene, the description's materials, quads and
+ *           spheres added in order through pt_v4_add_material / _add_quad / _add_sphere,
+ *           pt_v4_set_camera(&cams[v]) and pt_v4_render_device leave on that slice.
+ * The process-wide scene, camera and v4 frame counter are neither read nor changed; scenes, cams and
+ * scene_of_view are consumed before the call returns.  The scene tables are built on the host with the
+ * code behind pt_v4_add_*; they travel to the device through a ring of four tables that grow to the
+ * largest batch seen.  Checked before any GPU work -- PT_EINVAL: everything pt_v4_render_device_views
+ * rejects, scenes NULL, nscenes outside [1, PT_V4_MAX_VIEWS], scene_of_view NULL with nscenes != nviews,
+ * a mapping entry outside [0, nscenes) (pt_last_error names the view), a description with a negative
+ * count, nquads + nspheres > PT_V4_MAX_OBJECTS or nmaterials > PT_V4_MAX_OBJECTS (pt_last_error names
+ * the scene).  Coordinates that are not finite are accepted as pt_v4_add_* accepts them (such a scene
+ * only has no sky window); a scene without objects is valid. */
+int pt_v4_render_device_scenes(const pt_device_job* job, const pt_v4_scene_desc* scenes, int32_t nscenes,
+                               const pt_v4_camera* cams, const int32_t* scene_of_view, int32_t nviews,
+                               uint32_t* pixels, int32_t format, void* hip_stream);
 int pt_v4_count_device(const pt_device_job* job, void* hip_stream, pt_work_counts* out);   /* sync */
 
 /* --- tile work queue: the host tile scheduler, on the GPU ------------------------
