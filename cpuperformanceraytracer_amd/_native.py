@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "pt_v4_add_quad", "pt_v4_add_sphere", "pt_v4_set_frame", "pt_v4_get_frame", "pt_v4_get_scene_tables", "pt_render_opt_v4",
     "pt_copy_output_to_file", "pt_v4_render_device", "pt_v4_render_device_chain", "pt_v4_render_device_present",
     "pt_v4_render_device_views", "pt_v4_render_device_scenes", "pt_v4_get_scene_desc", "pt_v4_count_device", "pt_v4_begin_frame",
+    "pt_v4_make_env_set", "pt_v4_free_env_set", "pt_v4_render_device_envs",
     "pt_v4_default_camera", "pt_v4_set_camera", "pt_v4_get_camera", "pt_v4_get_sky_window",
     "pt_make_work_queue", "pt_add_work_queue_entry", "pt_complete_all_work", "pt_complete_all_work_async",
     "pt_wait_work", "pt_work_queue_size", "pt_free_work_queue",
@@ -215,6 +216,10 @@ def load() -> ctypes.CDLL:
         "pt_v4_render_device_scenes": (i32, [ctypes.POINTER(PtDeviceJob), ctypes.POINTER(PtV4SceneDesc), i32,
                                              ctypes.POINTER(PtV4Camera), ctypes.POINTER(i32), i32, vp, i32, vp]),
         "pt_v4_get_scene_desc": (i32, [ctypes.POINTER(PtV4SceneDesc)]),
+        "pt_v4_make_env_set": (i32, [ctypes.POINTER(PtTexture), i32, ctypes.POINTER(vp)]),
+        "pt_v4_free_env_set": (None, [vp]),
+        "pt_v4_render_device_envs": (i32, [ctypes.POINTER(PtDeviceJob), vp, ctypes.POINTER(i32), ctypes.POINTER(PtV4SceneDesc), i32,
+                                           ctypes.POINTER(i32), ctypes.POINTER(PtV4Camera), i32, vp, i32, vp]),
         "pt_v4_count_device": (i32, [ctypes.POINTER(PtDeviceJob), vp, ctypes.POINTER(PtWorkCounts)]),
         "pt_v4_begin_frame": (i32, []),
         "pt_v4_default_camera": (None, [ctypes.POINTER(PtV4Camera)]),

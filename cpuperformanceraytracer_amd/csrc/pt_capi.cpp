@@ -29,6 +29,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -149,7 +150,8 @@ struct Dev {
     } views[kViewRing];
     unsigned views_next = 0;
     // scenes launches (pt_v4_render_device_scenes): the same ring rule for one block per slot that holds
-    // the launch's scene records, its view table and its view -> scene mapping, in that order.  A block
+    // the launch's scene records, its view table, its view -> scene mapping and (an envs launch,
+    // pt_v4_render_device_envs) its view -> texture mapping, in that order.  A block
     // has the size its largest launch so far needed (a record is ~2 KiB: 1024 of them ~2 MiB), grown
     // only after the slot's event completed.
     struct SceneSlot {
@@ -194,6 +196,19 @@ struct Mirror {
     bool valid = false;                 // deferred mode: the device copies are authoritative
 };
 
+}  // namespace
+
+// An env set (include/pt_mi355.h): `count` textures resident on one device, and their record table.
+struct pt_v4_env_set {
+    Dev* dev = nullptr;                 // the device of views and scenes launches that holds it
+    unsigned char* block = nullptr;     // the one device allocation: table, then texels
+    const PtV4EnvRec* table = nullptr;  // == block
+    int32_t count = 0;
+    pt_v4_env_set* next = nullptr;      // State::env_sets
+};
+
+namespace {
+
 struct State {
     bool inited = false;
     pt_config cfg{};
@@ -206,6 +221,7 @@ struct State {
     const float* env_src = nullptr;     // host data the device copies were made from
     int32_t env_w = 0, env_h = 0;
     bool have_env = false;
+    pt_v4_env_set* env_sets = nullptr;  // the live env sets (pt_v4_make_env_set), newest first
     // PT_FLAG_PIN_HOST (one device): the registered host buffer, copy streams and band events
     const float* pinned = nullptr;
     size_t pinned_bytes = 0;
@@ -401,6 +417,7 @@ const char* guard_name(uint32_t id)
         case PT_G_QUEUE_GROUP: return "queue group out of range";
         case PT_G_VIEW: return "views launch: view index beyond the view table";
         case PT_G_SCENE: return "scenes launch: scene index beyond the scene table, or a record's object counts beyond MAX_OBJECTS";
+        case PT_G_ENV: return "envs launch: env index beyond the env set, or a record's width or height not positive";
         case PT_G_CAM_INDEX: return "camera-hit cache record outside the geometry's tiles";
         case PT_G_CAM_RECORD: return "a traced camera hit differs from its cached record; value: tile * 64 + lane";
         case PT_G_CHAIN_WAIT: return "chained launch: the previous launch's tile never became ready; value: the tile | its epoch's lag "
@@ -1419,6 +1436,30 @@ int upload_env(const pt_texture* t)
     return PT_OK;
 }
 
+// ---- env sets (pt_v4_make_env_set; pt_v4.h PtV4Envs) ----
+// One device allocation per set: the table of `count` PtV4EnvRec at its start, then the texels of every
+// texture in index order, each on a 256-byte boundary.  Immutable after its one upload.
+bool env_set_live(const pt_v4_env_set* s)
+{
+    for (const pt_v4_env_set* p = g.env_sets; p; p = p->next)
+        if (p == s) return true;
+    return false;
+}
+
+// unlink and free a live set (its device's stream is synchronised first: no launch reads it any more)
+void release_env_set(pt_v4_env_set* s)
+{
+    for (pt_v4_env_set** p = &g.env_sets; *p; p = &(*p)->next)
+        if (*p == s) {
+            *p = s->next;
+            break;
+        }
+    (void)use_dev(*s->dev);
+    (void)hipStreamSynchronize(s->dev->stream);
+    (void)hipFree(s->block);
+    delete s;
+}
+
 // RenderTile argument checks (simd_tiled.cpp:489-535 assumptions; Application.cpp:36-94)
 int check_tile(const pt_buffer_info* b, const pt_tile_info* t)
 {
@@ -1796,6 +1837,7 @@ void pt_shutdown(void)
 {
     if (!g.inited) return;
     DeviceGuard guard;
+    while (g.env_sets) release_env_set(g.env_sets);
     for (int d = 0; d < g.ndev; ++d) free_dev(g.dev[d]);
     if (g.ndev > 0) (void)hipSetDevice(g.cfg.devices[0]);
     unpin();
@@ -1866,6 +1908,66 @@ int pt_set_env_map(const pt_texture* tex)
         return PT_OK;
     }
     return upload_env(tex);
+}
+
+int pt_v4_make_env_set(const pt_texture* texs, int32_t n, pt_v4_env_set** out)
+{
+    int rc;
+    if (!texs) return fail(PT_EINVAL, "null texture array");
+    if (!out) return fail(PT_EINVAL, "null env set result");
+    if (n < 1 || n > PT_V4_MAX_VIEWS) return fail(PT_EINVAL, "%d textures outside [1, %d]", n, PT_V4_MAX_VIEWS);
+    const auto up256 = [](size_t b) { return (b + 255u) & ~(size_t)255u; };
+    std::vector<size_t> off((size_t)n);
+    size_t bytes = up256((size_t)n * sizeof(PtV4EnvRec));
+    for (int32_t i = 0; i < n; ++i) {
+        if ((rc = check_texture(&texs[i]))) {
+            char why[400];
+            snprintf(why, sizeof(why), "%s", g_err);
+            return fail(rc, "texture %d: %s", i, why);
+        }
+        off[(size_t)i] = bytes;
+        bytes += up256((size_t)texs[i].width * texs[i].height * 3 * sizeof(float));
+    }
+    if ((rc = ensure_init())) return rc;
+    DeviceGuard guard;
+    Dev& dv = g.dev[0];
+    if ((rc = use_dev(dv))) return rc;
+    // staged on the host, so that table and texels travel in one copy
+    std::unique_ptr<unsigned char[]> host(new (std::nothrow) unsigned char[bytes]);
+    std::unique_ptr<pt_v4_env_set> set(new (std::nothrow) pt_v4_env_set);
+    if (!host || !set) return fail(PT_ENOMEM, "no host memory to stage an env set of %zu bytes", bytes);
+    if (hipMalloc((void**)&set->block, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PT_ENOMEM, "hipMalloc(env set, %zu bytes) failed on device %d", bytes, dv.ordinal);
+    }
+    memset(host.get(), 0, off[0]);
+    PtV4EnvRec* const rec = reinterpret_cast<PtV4EnvRec*>(host.get());
+    for (int32_t i = 0; i < n; ++i) {
+        const size_t tb = (size_t)texs[i].width * texs[i].height * 3 * sizeof(float);
+        rec[i] = PtV4EnvRec{reinterpret_cast<const float*>(set->block + off[(size_t)i]), texs[i].width, texs[i].height};
+        memcpy(host.get() + off[(size_t)i], texs[i].data, tb);
+        memset(host.get() + off[(size_t)i] + tb, 0, up256(tb) - tb);
+    }
+    hipError_t e = hipMemcpyAsync(set->block, host.get(), bytes, hipMemcpyHostToDevice, dv.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(dv.stream);
+    if (e != hipSuccess) {
+        (void)hipFree(set->block);
+        return fail(PT_EHIP, "env set upload failed: %s", hipGetErrorString(e));
+    }
+    set->dev = &dv;
+    set->table = reinterpret_cast<const PtV4EnvRec*>(set->block);
+    set->count = n;
+    set->next = g.env_sets;
+    g.env_sets = set.get();
+    *out = set.release();
+    return PT_OK;
+}
+
+void pt_v4_free_env_set(pt_v4_env_set* set)
+{
+    if (!set || !env_set_live(set)) return;   // (NULL, freed already, or released by pt_shutdown)
+    DeviceGuard guard;
+    release_env_set(set);
 }
 
 static int ensure_env(const pt_texture* tex)
@@ -2705,8 +2807,12 @@ int pt_v4_get_scene_desc(pt_v4_scene_desc* out)
 // alone).  Each record is pt_v4_build_scene of its description -- the code behind pt_v4_add_* -- and each
 // view's window pt_v4_skywin_build of (its scene, its camera).  Records, view table and mapping travel in
 // one block of the device's scene ring (Dev::scenes).
-int pt_v4_render_device_scenes(const pt_device_job* dj, const pt_v4_scene_desc* scenes, int32_t nscenes, const pt_v4_camera* cams,
-                               const int32_t* scene_of_view, int32_t nviews, uint32_t* pixels, int32_t format, void* stream)
+// with_envs (pt_v4_render_device_envs): the texture per view as well -- view v reads record env_of_view[v]
+// of the env set's device table; the mapping travels at the end of the same block.  Then `scenes` may be
+// NULL: every view renders the current process-wide scene (the one thing of the process-wide state read).
+static int v4_scenes_launch(const pt_device_job* dj, bool with_envs, const pt_v4_env_set* envs, const int32_t* env_of_view,
+                            const pt_v4_scene_desc* scenes, int32_t nscenes, const int32_t* scene_of_view, const pt_v4_camera* cams,
+                            int32_t nviews, uint32_t* pixels, int32_t format, void* stream)
 {
     int rc;
     if (!dj) return fail(PT_EINVAL, "null device job");
@@ -2726,9 +2832,16 @@ int pt_v4_render_device_scenes(const pt_device_job* dj, const pt_v4_scene_desc* 
     std::vector<float> dist((size_t)nviews);
     for (int32_t v = 0; v < nviews; ++v)
         if ((rc = v4_check_camera(&cams[v], &dist[(size_t)v], v))) return rc;
+    const bool current_scene = with_envs && !scenes;
+    if (current_scene) {
+        if (nscenes != 0 || scene_of_view) return fail(PT_EINVAL, "no scenes (the current scene): nscenes must be 0 and scene_of_view NULL");
+        if ((rc = v4_ensure_scene())) return rc;   // (host only)
+        scenes = reinterpret_cast<const pt_v4_scene_desc*>(&g.v4desc);
+        nscenes = 1;
+    }
     if (!scenes) return fail(PT_EINVAL, "null scene array");
     if (nscenes < 1 || nscenes > PT_V4_MAX_VIEWS) return fail(PT_EINVAL, "nscenes %d outside [1, %d]", nscenes, PT_V4_MAX_VIEWS);
-    if (!scene_of_view && nscenes != nviews)
+    if (!scene_of_view && !current_scene && nscenes != nviews)
         return fail(PT_EINVAL, "no scene_of_view: view v uses scene v, but nscenes %d != nviews %d", nscenes, nviews);
     if (scene_of_view)
         for (int32_t v = 0; v < nviews; ++v)
@@ -2741,6 +2854,18 @@ int pt_v4_render_device_scenes(const pt_device_job* dj, const pt_v4_scene_desc* 
             d.nquads + d.nspheres > PT_V4_MAX_OBJECTS || d.nmat > PT_V4_MAX_OBJECTS)
             return fail(PT_EINVAL, "scene %d: %d quads + %d spheres, %d materials (each count >= 0; objects and materials <= %d)", s,
                         d.nquads, d.nspheres, d.nmat, PT_V4_MAX_OBJECTS);
+    }
+    if (with_envs) {
+        if (!envs) return fail(PT_EINVAL, "null env set");
+        if (!env_set_live(envs)) return fail(PT_EINVAL, "not a live env set (freed, or from before pt_shutdown)");
+        if (!env_of_view && envs->count != nviews)
+            return fail(PT_EINVAL, "no env_of_view: view v uses texture v, but the set has %d textures for %d views", envs->count, nviews);
+        if (env_of_view)
+            for (int32_t v = 0; v < nviews; ++v)
+                if (env_of_view[v] < 0 || env_of_view[v] >= envs->count)
+                    return fail(PT_EINVAL, "view %d: env_of_view %d outside [0, %d)", v, env_of_view[v], envs->count);
+        if (!dj->use_env || g.v4cfg.env_mode == PT_V4_ENV_NONE)
+            return fail(PT_EINVAL, "an envs launch needs an env term: use_env %d, v4 env mode %d", dj->use_env, g.v4cfg.env_mode);
     }
     if (dj->nframes == 0 || dj->nrows == 0) return PT_OK;   // nothing to render
 
@@ -2767,14 +2892,18 @@ int pt_v4_render_device_scenes(const pt_device_job* dj, const pt_v4_scene_desc* 
     j.accumulate = g.v4cfg.accumulate_frames;
     j.fast_exp = g.v4cfg.fast_exp;
     j.sky = PtV4SkyWin{-1, {}};   // (the views' records carry the cameras and the windows)
-    if (dj->use_env) {
+    if (with_envs) {
+        j.env_mode = g.v4cfg.env_mode;   // (job.env, env_w, env_h stay null: the views' records carry the textures)
+    } else if (dj->use_env) {
         if (g.v4cfg.env_mode == PT_V4_ENV_NONE) return fail(PT_ESTATE, "use_env with v4 env mode NONE");
         if ((rc = v4_use_env(j))) return rc;
     }
     if ((rc = dev_of(dj->buf, &dvp)) || (rc = use_dev(*dvp))) return rc;
     Dev& dv = *dvp;
+    if (with_envs && envs->dev != dvp)
+        return fail(PT_EINVAL, "the env set lives on device %d, the job's buffer on device %d", envs->dev->ordinal, dv.ordinal);
     hipStream_t st = (hipStream_t)stream;
-    if (j.env_mode != PT_V4_ENV_NONE) j.env = dv.denv;
+    if (!with_envs && j.env_mode != PT_V4_ENV_NONE) j.env = dv.denv;
     j.err = dv.derr;
     // the render kernel writes the pixels with the default tonemap pair; any other pair: a second pass
     const bool fused = pixels && g.v4cfg.fast_aces && g.v4cfg.fast_gamma;
@@ -2783,7 +2912,8 @@ int pt_v4_render_device_scenes(const pt_device_job* dj, const pt_v4_scene_desc* 
     const auto up16 = [](size_t n) { return (n + 15u) & ~(size_t)15u; };
     const size_t off_views = up16((size_t)nscenes * sizeof(PtV4SceneRec));
     const size_t off_map = off_views + up16((size_t)nviews * sizeof(PtV4View));
-    const size_t need = off_map + up16((size_t)nviews * sizeof(int32_t));
+    const size_t off_emap = off_map + up16((size_t)nviews * sizeof(int32_t));
+    const size_t need = off_emap + (with_envs ? up16((size_t)nviews * sizeof(int32_t)) : 0u);
     Dev::SceneSlot& ss = dv.scenes[dv.scenes_next++ % kViewRing];
     if (!ss.done) HIP_TRY(hipEventCreateWithFlags(&ss.done, hipEventDisableTiming));
     if (ss.pending) {   // the slot's previous launch (kViewRing launches back) still reads the block: wait for it
@@ -2815,8 +2945,9 @@ int pt_v4_render_device_scenes(const pt_device_job* dj, const pt_v4_scene_desc* 
         memset(hrec[s].mx, 0, sizeof(hrec[s].mx));   // (the preparation kernel fills them on the device)
     }
     for (int32_t v = 0; v < nviews; ++v) {
-        const int32_t s = scene_of_view ? scene_of_view[v] : v;
+        const int32_t s = scene_of_view ? scene_of_view[v] : current_scene ? 0 : v;
         hmap[v] = s;
+        if (with_envs) reinterpret_cast<int32_t*>(ss.host + off_emap)[v] = env_of_view ? env_of_view[v] : v;
         PtV4View& r = hview[v];
         memcpy(r.cam_pos, cams[v].position, sizeof(r.cam_pos));
         r.cam_dist = dist[(size_t)v];
@@ -2830,8 +2961,14 @@ int pt_v4_render_device_scenes(const pt_device_job* dj, const pt_v4_scene_desc* 
     j.queue_next = ls.queue_next;
     const PtV4Views va{reinterpret_cast<const PtV4View*>(ss.dev + off_views), nviews, fused ? pixels : nullptr, g.v4_views_grid};
     const PtV4Scenes sa{reinterpret_cast<PtV4SceneRec*>(ss.dev), nscenes, reinterpret_cast<const int32_t*>(ss.dev + off_map)};
-    hipError_t e = pt_launch_v4_scenes(j, va, sa, st);
-    if (e != hipSuccess) return fail(PT_EHIP, "v4 scenes launch failed: %s", hipGetErrorString(e));
+    hipError_t e;
+    if (with_envs) {
+        const PtV4Envs ea{envs->table, envs->count, reinterpret_cast<const int32_t*>(ss.dev + off_emap)};
+        e = pt_launch_v4_envs(j, va, sa, ea, st);
+    } else {
+        e = pt_launch_v4_scenes(j, va, sa, st);
+    }
+    if (e != hipSuccess) return fail(PT_EHIP, "v4 %s launch failed: %s", with_envs ? "envs" : "scenes", hipGetErrorString(e));
     HIP_TRY(hipEventRecord(ss.done, st));
     ss.pending = true;
     if ((rc = queue_done(dv, ls.slot, st, true))) return rc;
@@ -2842,6 +2979,19 @@ int pt_v4_render_device_scenes(const pt_device_job* dj, const pt_v4_scene_desc* 
         if (e != hipSuccess) return fail(PT_EHIP, "tonemap launch failed: %s", hipGetErrorString(e));
     }
     return PT_OK;
+}
+
+int pt_v4_render_device_scenes(const pt_device_job* dj, const pt_v4_scene_desc* scenes, int32_t nscenes, const pt_v4_camera* cams,
+                               const int32_t* scene_of_view, int32_t nviews, uint32_t* pixels, int32_t format, void* stream)
+{
+    return v4_scenes_launch(dj, false, nullptr, nullptr, scenes, nscenes, scene_of_view, cams, nviews, pixels, format, stream);
+}
+
+int pt_v4_render_device_envs(const pt_device_job* dj, const pt_v4_env_set* envs, const int32_t* env_of_view,
+                             const pt_v4_scene_desc* scenes, int32_t nscenes, const int32_t* scene_of_view, const pt_v4_camera* cams,
+                             int32_t nviews, uint32_t* pixels, int32_t format, void* stream)
+{
+    return v4_scenes_launch(dj, true, envs, env_of_view, scenes, nscenes, scene_of_view, cams, nviews, pixels, format, stream);
 }
 
 int pt_v4_count_device(const pt_device_job* dj, void* stream, pt_work_counts* out)

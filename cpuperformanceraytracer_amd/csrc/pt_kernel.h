@@ -111,6 +111,8 @@ enum PtGuardId : uint32_t {
     PT_G_VIEW = 16,         // a views launch: a tile entry's view index beyond the view table
     PT_G_SCENE = 17,        // a scenes launch: a view's scene index beyond the scene table, or (value | 2^31) a
                             // scene record whose object counts exceed PT_V4_MAX_OBJECTS
+    PT_G_ENV = 18,          // an envs launch: a view's env index beyond the env set, or (value | 2^31) an env
+                            // record whose width or height is not positive
 };
 
 // Tile queues: one counter per XCD group, 128 B apart (PT_QUEUE_WORDS u32 per launch).

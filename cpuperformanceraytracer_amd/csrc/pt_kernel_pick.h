@@ -280,3 +280,24 @@ constexpr PtKeyList<PtV4ScenesKey, kPtV4ScenesKeyCount> pt_v4_scenes_key_list()
     return l;
 }
 constexpr PtKeyList<PtV4ScenesKey, kPtV4ScenesKeyCount> kPtV4ScenesKeys = pt_v4_scenes_key_list();
+
+// ---- v4 envs (pt_v4.hip pt_v4_envs_kernel <env, layout, fexp>) ----
+// A batch of env maps runs the scenes form with the texture as a per-view record.  It has no meaning
+// without an env term, so ENV is equirect or cubemap: 8 keys, in a list of its own.
+struct PtV4EnvsKey {
+    int env, layout, fexp;
+    constexpr bool operator==(const PtV4EnvsKey& o) const { return env == o.env && layout == o.layout && fexp == o.fexp; }
+};
+constexpr bool pt_pick_v4_envs_valid(int env, int layout) { return env >= 1 && env < 3 && layout >= 0 && layout < kPickTiled; }
+constexpr PtV4EnvsKey pt_pick_v4_envs_key(int env, int layout, bool fast_exp) { return {env, layout, fast_exp ? 1 : 0}; }
+constexpr size_t kPtV4EnvsKeyCount = 2 * 2 * 2;
+constexpr PtKeyList<PtV4EnvsKey, kPtV4EnvsKeyCount> pt_v4_envs_key_list()
+{
+    PtKeyList<PtV4EnvsKey, kPtV4EnvsKeyCount> l{};
+    size_t n = 0;
+    for (int env = 1; env < 3; ++env)
+        for (int layout = 0; layout < kPickTiled; ++layout)
+            for (int fexp = 1; fexp >= 0; --fexp) l.k[n++] = {env, layout, fexp};
+    return l;
+}
+constexpr PtKeyList<PtV4EnvsKey, kPtV4EnvsKeyCount> kPtV4EnvsKeys = pt_v4_envs_key_list();

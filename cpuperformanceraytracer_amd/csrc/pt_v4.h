@@ -172,3 +172,24 @@ struct PtV4Scenes {
 // FEXP) of pt_v4_scenes_kernel, launched as pt_launch_v4_views launches its own (unscheduled, a plain
 // launch, views.grid_cap honoured).
 hipError_t pt_launch_v4_scenes(const PtV4Job& job, const PtV4Views& views, const PtV4Scenes& scenes, hipStream_t stream);
+
+// ---- a batch of env maps in one launch (pt_v4_render_device_envs; pt_v4.hip pt_v4_envs_kernel) ----
+// A scenes launch whose views each name a texture of an env set (pt_capi.cpp pt_v4_env_set): the texture
+// is a record of a device table instead of job.env / env_w / env_h, which are not read.  View v's texture
+// is env_of_view[v] (a parallel array of the view table, like scene_of_view).  The record is read through
+// the constant address space at a wave-uniform address -- pointer, width and height together -- when the
+// wave takes a tile; how it is sampled (equirect / stacked cubemap) stays job.env_mode.
+struct PtV4EnvRec {
+    const float* data;   // device texels, H x W x 3 f32
+    int32_t w, h;
+};
+static_assert(sizeof(PtV4EnvRec) == 16, "an env record is 16 B");
+struct PtV4Envs {
+    const PtV4EnvRec* table;       // device memory, nenvs records, immutable while the set lives
+    int32_t nenvs;
+    const int32_t* env_of_view;    // device memory, one entry per view, each in [0, nenvs)
+};
+// pt_launch_v4_scenes with the texture per view: the instances (ENV equirect / cubemap x row layout x FEXP)
+// of pt_v4_envs_kernel.  job.env_mode is not NONE; job.env, env_w and env_h are not read.
+hipError_t pt_launch_v4_envs(const PtV4Job& job, const PtV4Views& views, const PtV4Scenes& scenes, const PtV4Envs& envs,
+                             hipStream_t stream);

@@ -1,7 +1,7 @@
 // pt_v4_tile_pool.inc -- the body of the v4 per-tile pool kernels (pt_v4.hip includes it inside
-// pt_v4_kernel, pt_v4_views_kernel and pt_v4_scenes_kernel, which declare ENV, LAYOUT, COUNT, DEF, FEXP,
-// DFL, PRESENT, VIEWS, SCENES, the kernel arguments job and sc, `cam`, the views arguments `va`, the scenes
-// arguments `sa` and the view's scene `srec`).
+// pt_v4_kernel, pt_v4_views_kernel, pt_v4_scenes_kernel and pt_v4_envs_kernel, which declare ENV, LAYOUT,
+// COUNT, DEF, FEXP, DFL, PRESENT, VIEWS, SCENES, ENVS, the kernel arguments job and sc, `cam`, the views
+// arguments `va`, the scenes arguments `sa`, the view's scene `srec` and the envs arguments `ea`).
     // SCENES: no block-wide material table (each wave follows its own view's scene: srec.mat / srec.mx).
     // SLDS (the A/B build PT_V4_SCENES_LDS=1): a table per wave in LDS, refilled when the wave takes a tile,
     // paid for by a shorter env miss queue, so that the block stays within 25 LDS granules.
@@ -33,7 +33,7 @@
     const int ntiles = tiles_x * ((job.nrows + 7) >> 3);
     float* const col = s_col[wv];
     const size_t cs = (LAYOUT == PT_LAYOUT_INTERLEAVED) ? 1u : 8u;
-    const Tex tex{job.env, job.env_w, job.env_h};
+    Tex tex{job.env, job.env_w, job.env_h};   // (ENVS: the tile's view's texture, taken below; the job's is null)
     const bool random = DFL || job.random_jitter != 0, rejection = DFL || job.rejection != 0;
     const int B = job.num_bounces;
     const float W = (float)job.width, H = (float)job.height;
@@ -87,6 +87,19 @@
             srec.mat = s_mat + wv * PT_V4_MAX_OBJECTS;
             srec.mx = s_mx + wv * PT_V4_MAX_OBJECTS;
         }
+    }
+    if constexpr (ENVS) {
+        // and so is the texture: pointer, width and height are replaced together, from one record read
+        // through the constant address space at a wave-uniform address (scalar loads, scalar registers;
+        // texel_at / texel_rn clamp with w * h, so dimensions of another texture would index past this one).
+        // Invariant: no deferred miss survives a tile.  The entries of s_qd / s_qt carry a direction, an rng
+        // and a slot but no texture; `resolve` reads this wave's current `tex`.  That is right only because
+        // every chunk ends with drain(qn), before the wave leaves the tile and comes back here.
+        uint32_t env = (uint32_t)((const __attribute__((address_space(4))) int32_t*)ea.env_of_view)[view];
+        if (!PT_GUARD(job.err, env < (uint32_t)ea.nenvs, PT_G_ENV, env)) env = 0;   // (checked build: reported)
+        const __attribute__((address_space(4))) PtV4EnvRec* const er = (const __attribute__((address_space(4))) PtV4EnvRec*)(ea.table + env);
+        tex = Tex{er->data, er->w, er->h};
+        if (!PT_GUARD(job.err, tex.w > 0 && tex.h > 0, PT_G_ENV, 0x80000000u | env)) tex.w = tex.h = 1;
     }
     const int tcol = (vtile % tiles_x) * 8, trow = (vtile / tiles_x) * 8;
     uint32_t tile_work = 1;   // pool iterations of this tile (the schedule's cost)

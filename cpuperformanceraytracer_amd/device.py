@@ -323,6 +323,97 @@ def render_v4_device_scenes(buf, scenes, cameras, width: int, height: int, scene
                                                 _stream(stream)), "pt_v4_render_device_scenes")
 
 
+class V4EnvSet:
+    """An env set (pt_v4_make_env_set): textures resident in device memory until close() or garbage
+    collection.  pt_shutdown releases every set; closing one after that is harmless."""
+
+    def __init__(self, handle: int, count: int):
+        self._handle, self.count = handle, count
+
+    def __len__(self) -> int:
+        return self.count
+
+    @property
+    def handle(self) -> int:
+        if not self._handle:
+            raise N.PtError(N.PT_EINVAL, "V4EnvSet", "the env set is closed")
+        return self._handle
+
+    def close(self) -> None:
+        if self._handle:
+            N.load().pt_v4_free_env_set(self._handle)
+            self._handle = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # (interpreter teardown)
+            pass
+
+
+def make_v4_env_set(textures) -> V4EnvSet:
+    """Upload a list of H x W x 3 float32 arrays (shapes may differ) as one env set, once; each is read as the
+    v4_config's env_mode says at render time (equirect, or six cubemap faces stacked).  Synchronous."""
+    from .renderer import _pt_texture
+    pairs = [_pt_texture(t) for t in textures]
+    if not pairs:
+        raise N.PtError(N.PT_EINVAL, "make_v4_env_set", "no textures")
+    arr = (N.PtTexture * len(pairs))(*[p for p, _ in pairs])
+    out = ctypes.c_void_p()
+    N.check(N.load().pt_v4_make_env_set(arr, len(pairs), ctypes.byref(out)), "pt_v4_make_env_set")
+    del pairs
+    return V4EnvSet(out.value, len(arr))
+
+
+def render_v4_device_envs(buf, envs: V4EnvSet, cameras, width: int, height: int, env_of_view=None, scenes=None,
+                          scene_of_view=None, *, frame_first: int, nframes: int, num_bounces: int = 8, row_start: int = 0,
+                          row_stride: int = 1, nrows: int | None = None, layout: int = N.PT_LAYOUT_INTERLEAVED,
+                          use_env: bool = True, pixels=None, pixel_format: int = N.PT_PIXEL_RGBA8, stream=None) -> None:
+    """A batch of env maps in one launch (pt_v4_render_device_envs): render_v4_device_scenes with a texture per
+    view.  View v reads texture env_of_view[v] of `envs` (make_v4_env_set) -- texture v when env_of_view is
+    None, which needs as many textures as cameras -- and renders scenes[scene_of_view[v]], or the current
+    scene when `scenes` is None.  Slice v of `buf` ends bit for bit as set_env_map(that texture), that scene
+    built through ClearScene + Add*ToScene, v4_camera(*cameras[v]) and render_v4_device on it would leave it;
+    the env map of set_env_map, the scene, the camera and the v4 frame counter are not changed.  Asynchronous
+    on `stream`."""
+    nrows = height if nrows is None else nrows
+    cams = [(tuple(float(x) for x in pos), float(fov)) for pos, fov in cameras]
+    nviews = len(cams)
+    if any(len(pos) != 3 for pos, _ in cams):
+        raise N.PtError(N.PT_EINVAL, "render_v4_device_envs", "a camera position has three components")
+    if not 1 <= nviews <= N.PT_V4_MAX_VIEWS:
+        raise N.PtError(N.PT_EINVAL, "render_v4_device_envs", f"{nviews} cameras outside [1, {N.PT_V4_MAX_VIEWS}]")
+    job = _job(buf, width, height, row_start, row_stride, nviews * nrows, frame_first, nframes, num_bounces, layout, use_env)
+    job.nrows = nrows
+    if pixels is not None:
+        _check_pixels(pixels, nviews * nrows * width, buf)
+    arr = (N.PtV4Camera * nviews)(*[N.PtV4Camera((ctypes.c_float * 3)(*pos), fov) for pos, fov in cams])
+
+    def mapping(m, what):
+        if m is None:
+            return None
+        if len(m) != nviews:
+            raise N.PtError(N.PT_EINVAL, "render_v4_device_envs", f"{what} has {len(m)} entries for {nviews} views")
+        return (ctypes.c_int32 * nviews)(*[int(x) for x in m])
+    sarr, nscenes = None, 0
+    if scenes is not None:
+        descs = [v4_scene_desc(s) for s in scenes]
+        if not descs:
+            raise N.PtError(N.PT_EINVAL, "render_v4_device_envs", "no scenes")
+        sarr, nscenes = (N.PtV4SceneDesc * len(descs))(*descs), len(descs)
+    N.check(N.load().pt_v4_render_device_envs(ctypes.byref(job), envs.handle if envs is not None else None,
+                                              mapping(env_of_view, "env_of_view"), sarr, nscenes,
+                                              mapping(scene_of_view, "scene_of_view"), arr, nviews,
+                                              pixels.data_ptr() if pixels is not None else None, pixel_format,
+                                              _stream(stream)), "pt_v4_render_device_envs")
+
+
 def count_v4_device(buf, width: int, height: int, *, frame_first: int, nframes: int, num_bounces: int = 8,
                     row_start: int = 0, row_stride: int = 1, nrows: int | None = None,
                     layout: int = N.PT_LAYOUT_INTERLEAVED, use_env: bool = False, stream=None) -> dict:

@@ -393,6 +393,42 @@ int pt_v4_get_scene_desc(pt_v4_scene_desc* out);
 int pt_v4_render_device_scenes(const pt_device_job* job, const pt_v4_scene_desc* scenes, int32_t nscenes,
                                const pt_v4_camera* cams, const int32_t* scene_of_view, int32_t nviews,
                                uint32_t* pixels, int32_t format, void* hip_stream);
+/* A batch of ENV MAPS in one launch: a view is (camera, scene, environment), each chosen per view.
+ * An env set is a group of textures uploaded once and resident in device memory until freed, so that no
+ * texel travels per launch.
+ *   pt_v4_make_env_set  needs pt_init, as pt_set_env_map does.  n in [1, PT_V4_MAX_VIEWS]; every texture
+ *           as pt_set_env_map takes it (data, width, height > 0, 3 components; pt_last_error names the
+ *           offending index); shapes may differ.  How a texture is read -- equirect or six stacked cubemap
+ *           faces -- is not a property of the set: pt_v4_config.env_mode decides at render time, as for
+ *           pt_set_env_map's texture.  All texels go into one device allocation in index order, each
+ *           texture on a 256-byte boundary, with a table of n records {data, w, h}; one upload, then a
+ *           sync: on return the set is usable and `texs` no longer needed.  The set lives on the first
+ *           device of pt_init's list, where views and scenes launches of a one-device setup run.
+ *           PT_EINVAL / PT_ENOMEM: *out untouched, nothing leaked.
+ *   pt_v4_free_env_set  synchronises that device's stream, then frees.  NULL, or a set already freed: no-op.
+ *           pt_shutdown releases every live set; a handle from before pt_shutdown must not be used again.
+ *   pt_v4_render_device_envs  is pt_v4_render_device_scenes with a texture per view: view v reads texture
+ *           env_of_view[v] of `envs`; env_of_view == NULL means view v uses texture v and requires the
+ *           set's count == nviews.  scenes == NULL means every view renders the current process-wide scene
+ *           (the code behind pt_v4_get_scene_desc); then nscenes must be 0 and scene_of_view NULL.
+ *           Everything else as the scenes call: slices, pixels / format, limits, the nframes == 0 /
+ *           nrows == 0 shortcut, asynchrony, it ends a live chain, no chained or counting form.
+ *   result  view v's slice is bit for bit what pt_set_env_map(&texs[env_of_view[v]]), that view's scene
+ *           built through pt_v4_clear_scene + pt_v4_add_*, pt_v4_set_camera(&cams[v]) and
+ *           pt_v4_render_device leave on that slice.
+ * The process-wide env map, scene, camera and v4 frame counter are neither read nor changed (except that
+ * scenes == NULL reads the current scene).  Checked before any GPU work -- PT_EINVAL: everything the
+ * scenes call rejects, envs NULL or not a live set, a mapping entry outside [0, count) (pt_last_error
+ * names the view), env_of_view NULL with count != nviews, job->use_env == 0 or env_mode PT_V4_ENV_NONE
+ * (the call has no meaning without an env term), scenes NULL with nscenes != 0 or scene_of_view != NULL;
+ * and a buffer on another device than the set's. */
+typedef struct pt_v4_env_set pt_v4_env_set;
+int pt_v4_make_env_set(const pt_texture* texs, int32_t n, pt_v4_env_set** out);
+void pt_v4_free_env_set(pt_v4_env_set* set);
+int pt_v4_render_device_envs(const pt_device_job* job, const pt_v4_env_set* envs, const int32_t* env_of_view,
+                             const pt_v4_scene_desc* scenes, int32_t nscenes, const int32_t* scene_of_view,
+                             const pt_v4_camera* cams, int32_t nviews, uint32_t* pixels, int32_t format,
+                             void* hip_stream);
 int pt_v4_count_device(const pt_device_job* job, void* hip_stream, pt_work_counts* out);   /* sync */
 
 /* --- tile work queue: the host tile scheduler, on the GPU ------------------------
