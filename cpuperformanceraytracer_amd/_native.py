@@ -46,7 +46,7 @@ EXPORTED_SYMBOLS = (
     "pt_v4_add_quad", "pt_v4_add_sphere", "pt_v4_set_frame", "pt_v4_get_frame", "pt_v4_get_scene_tables", "pt_render_opt_v4",
     "pt_copy_output_to_file", "pt_v4_render_device", "pt_v4_render_device_chain", "pt_v4_render_device_present",
     "pt_v4_render_device_views", "pt_v4_render_device_scenes", "pt_v4_get_scene_desc", "pt_v4_count_device", "pt_v4_begin_frame",
-    "pt_v4_make_env_set", "pt_v4_free_env_set", "pt_v4_render_device_envs",
+    "pt_v4_make_env_set", "pt_v4_free_env_set", "pt_v4_render_device_envs", "pt_v4_render_device_batch",
     "pt_v4_default_camera", "pt_v4_set_camera", "pt_v4_get_camera", "pt_v4_get_sky_window",
     "pt_make_work_queue", "pt_add_work_queue_entry", "pt_complete_all_work", "pt_complete_all_work_async",
     "pt_wait_work", "pt_work_queue_size", "pt_free_work_queue",
@@ -125,6 +125,19 @@ class PtV4SceneDesc(ctypes.Structure):
     _fields_ = [("nquads", ctypes.c_int32), ("nspheres", ctypes.c_int32), ("nmaterials", ctypes.c_int32),
                 ("quads", (ctypes.c_float * 12) * PT_V4_MAX_OBJECTS), ("spheres", (ctypes.c_float * 4) * PT_V4_MAX_OBJECTS),
                 ("materials", PtV4Material * PT_V4_MAX_OBJECTS)]
+
+
+class PtV4FrameRange(ctypes.Structure):
+    """pt_v4_frame_range: a view's own frames [frame_first, frame_first + nframes)."""
+    _fields_ = [("frame_first", ctypes.c_uint32), ("nframes", ctypes.c_int32)]
+
+
+class PtV4Batch(ctypes.Structure):
+    """pt_v4_batch: everything per view (pt_v4_render_device_batch); every pointer but `cams` may be NULL."""
+    _fields_ = [("cams", ctypes.POINTER(PtV4Camera)), ("nviews", ctypes.c_int32), ("frames", ctypes.POINTER(PtV4FrameRange)),
+                ("scenes", ctypes.POINTER(PtV4SceneDesc)), ("nscenes", ctypes.c_int32), ("scene_of_view", ctypes.POINTER(ctypes.c_int32)),
+                ("envs", ctypes.c_void_p), ("env_of_view", ctypes.POINTER(ctypes.c_int32)), ("pixels", ctypes.c_void_p),
+                ("format", ctypes.c_int32)]
 
 
 class PtError(RuntimeError):
@@ -220,6 +233,7 @@ def load() -> ctypes.CDLL:
         "pt_v4_free_env_set": (None, [vp]),
         "pt_v4_render_device_envs": (i32, [ctypes.POINTER(PtDeviceJob), vp, ctypes.POINTER(i32), ctypes.POINTER(PtV4SceneDesc), i32,
                                            ctypes.POINTER(i32), ctypes.POINTER(PtV4Camera), i32, vp, i32, vp]),
+        "pt_v4_render_device_batch": (i32, [ctypes.POINTER(PtDeviceJob), ctypes.POINTER(PtV4Batch), vp]),
         "pt_v4_count_device": (i32, [ctypes.POINTER(PtDeviceJob), vp, ctypes.POINTER(PtWorkCounts)]),
         "pt_v4_begin_frame": (i32, []),
         "pt_v4_default_camera": (None, [ctypes.POINTER(PtV4Camera)]),

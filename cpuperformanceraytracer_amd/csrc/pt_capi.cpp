@@ -418,6 +418,7 @@ const char* guard_name(uint32_t id)
         case PT_G_VIEW: return "views launch: view index beyond the view table";
         case PT_G_SCENE: return "scenes launch: scene index beyond the scene table, or a record's object counts beyond MAX_OBJECTS";
         case PT_G_ENV: return "envs launch: env index beyond the env set, or a record's width or height not positive";
+        case PT_G_FRAMES: return "batch launch: a view's frame range record is invalid; value: the view";
         case PT_G_CAM_INDEX: return "camera-hit cache record outside the geometry's tiles";
         case PT_G_CAM_RECORD: return "a traced camera hit differs from its cached record; value: tile * 64 + lane";
         case PT_G_CHAIN_WAIT: return "chained launch: the previous launch's tile never became ready; value: the tile | its epoch's lag "
@@ -2807,18 +2808,43 @@ int pt_v4_get_scene_desc(pt_v4_scene_desc* out)
 // alone).  Each record is pt_v4_build_scene of its description -- the code behind pt_v4_add_* -- and each
 // view's window pt_v4_skywin_build of (its scene, its camera).  Records, view table and mapping travel in
 // one block of the device's scene ring (Dev::scenes).
-// with_envs (pt_v4_render_device_envs): the texture per view as well -- view v reads record env_of_view[v]
-// of the env set's device table; the mapping travels at the end of the same block.  Then `scenes` may be
-// NULL: every view renders the current process-wide scene (the one thing of the process-wide state read).
-static int v4_scenes_launch(const pt_device_job* dj, bool with_envs, const pt_v4_env_set* envs, const int32_t* env_of_view,
-                            const pt_v4_scene_desc* scenes, int32_t nscenes, const int32_t* scene_of_view, const pt_v4_camera* cams,
-                            int32_t nviews, uint32_t* pixels, int32_t format, void* stream)
+// The three public calls are one function: `kind` says which call it is, and the arguments travel as a
+// pt_v4_batch (the scenes and envs calls fill one; they leave `frames` NULL and never read it).
+//   kEnvs   (pt_v4_render_device_envs): the texture per view as well -- view v reads record env_of_view[v]
+//           of the env set's device table; the mapping travels at the end of the same block.  Then `scenes`
+//           may be NULL: every view renders the current process-wide scene (the one thing of the
+//           process-wide state read).
+//   kBatch  (pt_v4_render_device_batch): the frame range per view as well -- `frames`, or the job's range
+//           for every view when it is NULL -- in a parallel array at the end of the same block, and the
+//           batch instances, which read nothing but that array for first frame and count.  A texture per
+//           view when `envs` is given; without a set but with an env term, the process-wide map travels as
+//           a one-record table in the block (with a mapping of zeros), so that the kernel reads a table
+//           either way.
+enum class V4BatchKind { kScenes, kEnvs, kBatch };
+
+static int v4_scenes_launch(const pt_device_job* dj, V4BatchKind kind, const pt_v4_batch& args, void* stream)
 {
+    const bool batch = kind == V4BatchKind::kBatch;
+    const bool with_envs = kind == V4BatchKind::kEnvs || (batch && args.envs);   // a texture per view, from an env set
+    const pt_v4_camera* const cams = args.cams;
+    const int32_t nviews = args.nviews;
+    const pt_v4_frame_range* const frames = batch ? args.frames : nullptr;
+    const pt_v4_scene_desc* scenes = args.scenes;
+    int32_t nscenes = args.nscenes;
+    const int32_t* const scene_of_view = args.scene_of_view;
+    const pt_v4_env_set* const envs = args.envs;
+    const int32_t* const env_of_view = args.env_of_view;
+    uint32_t* const pixels = args.pixels;
+    const int32_t format = args.format;
     int rc;
     if (!dj) return fail(PT_EINVAL, "null device job");
     {
         pt_device_job geo = *dj;   // (the geometry / frame checks, as v4_device_job's)
         geo.use_env = 0;
+        if (batch && frames) {     // (the job's own range is not read: each view's is checked below)
+            geo.frame_first = 1;
+            geo.nframes = 0;
+        }
         PtJob unused;
         if ((rc = device_job(&geo, &unused))) return rc;
     }
@@ -2832,7 +2858,7 @@ static int v4_scenes_launch(const pt_device_job* dj, bool with_envs, const pt_v4
     std::vector<float> dist((size_t)nviews);
     for (int32_t v = 0; v < nviews; ++v)
         if ((rc = v4_check_camera(&cams[v], &dist[(size_t)v], v))) return rc;
-    const bool current_scene = with_envs && !scenes;
+    const bool current_scene = (with_envs || batch) && !scenes;
     if (current_scene) {
         if (nscenes != 0 || scene_of_view) return fail(PT_EINVAL, "no scenes (the current scene): nscenes must be 0 and scene_of_view NULL");
         if ((rc = v4_ensure_scene())) return rc;   // (host only)
@@ -2855,6 +2881,8 @@ static int v4_scenes_launch(const pt_device_job* dj, bool with_envs, const pt_v4
             return fail(PT_EINVAL, "scene %d: %d quads + %d spheres, %d materials (each count >= 0; objects and materials <= %d)", s,
                         d.nquads, d.nspheres, d.nmat, PT_V4_MAX_OBJECTS);
     }
+    if (batch && envs && (!dj->use_env || g.v4cfg.env_mode == PT_V4_ENV_NONE))   // (before the set is looked at)
+        return fail(PT_EINVAL, "an env set needs an env term: use_env %d, v4 env mode %d", dj->use_env, g.v4cfg.env_mode);
     if (with_envs) {
         if (!envs) return fail(PT_EINVAL, "null env set");
         if (!env_set_live(envs)) return fail(PT_EINVAL, "not a live env set (freed, or from before pt_shutdown)");
@@ -2867,7 +2895,19 @@ static int v4_scenes_launch(const pt_device_job* dj, bool with_envs, const pt_v4
         if (!dj->use_env || g.v4cfg.env_mode == PT_V4_ENV_NONE)
             return fail(PT_EINVAL, "an envs launch needs an env term: use_env %d, v4 env mode %d", dj->use_env, g.v4cfg.env_mode);
     }
-    if (dj->nframes == 0 || dj->nrows == 0) return PT_OK;   // nothing to render
+    if (batch) {
+        if (!envs && env_of_view) return fail(PT_EINVAL, "no env set (the process-wide env map, or none): env_of_view must be NULL");
+        bool any = false;
+        for (int32_t v = 0; v < nviews; ++v) {
+            const pt_v4_frame_range r = frames ? frames[v] : pt_v4_frame_range{dj->frame_first, dj->nframes};
+            if (r.frame_first < 1 || r.nframes < 0 || (uint64_t)r.frame_first + (uint64_t)r.nframes > kMaxFrame)
+                return fail(PT_EINVAL, "view %d: frame range [%u, +%d) invalid", v, r.frame_first, r.nframes);
+            any = any || r.nframes > 0;
+        }
+        if (!any || dj->nrows == 0) return PT_OK;   // nothing to render
+    } else if (dj->nframes == 0 || dj->nrows == 0) {
+        return PT_OK;   // nothing to render
+    }
 
     Dev* dvp = nullptr;
     DeviceGuard guard;
@@ -2894,6 +2934,9 @@ static int v4_scenes_launch(const pt_device_job* dj, bool with_envs, const pt_v4
     j.sky = PtV4SkyWin{-1, {}};   // (the views' records carry the cameras and the windows)
     if (with_envs) {
         j.env_mode = g.v4cfg.env_mode;   // (job.env, env_w, env_h stay null: the views' records carry the textures)
+    } else if (batch) {
+        // use_env 0 or env mode NONE: the ambient; else pt_set_env_map's texture as the one record of a staged table
+        if (dj->use_env && (rc = v4_use_env(j))) return rc;
     } else if (dj->use_env) {
         if (g.v4cfg.env_mode == PT_V4_ENV_NONE) return fail(PT_ESTATE, "use_env with v4 env mode NONE");
         if ((rc = v4_use_env(j))) return rc;
@@ -2913,7 +2956,10 @@ static int v4_scenes_launch(const pt_device_job* dj, bool with_envs, const pt_v4
     const size_t off_views = up16((size_t)nscenes * sizeof(PtV4SceneRec));
     const size_t off_map = off_views + up16((size_t)nviews * sizeof(PtV4View));
     const size_t off_emap = off_map + up16((size_t)nviews * sizeof(int32_t));
-    const size_t need = off_emap + (with_envs ? up16((size_t)nviews * sizeof(int32_t)) : 0u);
+    const bool staged_env = batch && !with_envs && j.env_mode != PT_V4_ENV_NONE;
+    const size_t off_erec = off_emap + (with_envs || staged_env ? up16((size_t)nviews * sizeof(int32_t)) : 0u);
+    const size_t off_frames = off_erec + (staged_env ? up16(sizeof(PtV4EnvRec)) : 0u);
+    const size_t need = off_frames + (batch ? up16((size_t)nviews * sizeof(PtV4FrameRange)) : 0u);
     Dev::SceneSlot& ss = dv.scenes[dv.scenes_next++ % kViewRing];
     if (!ss.done) HIP_TRY(hipEventCreateWithFlags(&ss.done, hipEventDisableTiming));
     if (ss.pending) {   // the slot's previous launch (kViewRing launches back) still reads the block: wait for it
@@ -2948,11 +2994,16 @@ static int v4_scenes_launch(const pt_device_job* dj, bool with_envs, const pt_v4
         const int32_t s = scene_of_view ? scene_of_view[v] : current_scene ? 0 : v;
         hmap[v] = s;
         if (with_envs) reinterpret_cast<int32_t*>(ss.host + off_emap)[v] = env_of_view ? env_of_view[v] : v;
+        if (staged_env) reinterpret_cast<int32_t*>(ss.host + off_emap)[v] = 0;
+        if (batch)
+            reinterpret_cast<PtV4FrameRange*>(ss.host + off_frames)[v] =
+                frames ? PtV4FrameRange{frames[v].frame_first, frames[v].nframes} : PtV4FrameRange{dj->frame_first, dj->nframes};
         PtV4View& r = hview[v];
         memcpy(r.cam_pos, cams[v].position, sizeof(r.cam_pos));
         r.cam_dist = dist[(size_t)v];
         v4_sky_window_for(desc[s], cams[v].position, &r.sky);
     }
+    if (staged_env) *reinterpret_cast<PtV4EnvRec*>(ss.host + off_erec) = PtV4EnvRec{dv.denv, j.env_w, j.env_h};
     HIP_TRY(hipMemcpyAsync(ss.dev, ss.host, need, hipMemcpyHostToDevice, st));
 
     LaunchSched ls;
@@ -2962,13 +3013,20 @@ static int v4_scenes_launch(const pt_device_job* dj, bool with_envs, const pt_v4
     const PtV4Views va{reinterpret_cast<const PtV4View*>(ss.dev + off_views), nviews, fused ? pixels : nullptr, g.v4_views_grid};
     const PtV4Scenes sa{reinterpret_cast<PtV4SceneRec*>(ss.dev), nscenes, reinterpret_cast<const int32_t*>(ss.dev + off_map)};
     hipError_t e;
-    if (with_envs) {
+    if (batch) {
+        const int32_t* const emap = reinterpret_cast<const int32_t*>(ss.dev + off_emap);
+        const PtV4Envs ea = with_envs    ? PtV4Envs{envs->table, envs->count, emap}
+                            : staged_env ? PtV4Envs{reinterpret_cast<const PtV4EnvRec*>(ss.dev + off_erec), 1, emap}
+                                         : PtV4Envs{nullptr, 0, nullptr};
+        e = pt_launch_v4_batch(j, va, sa, ea, PtV4Frames{reinterpret_cast<const PtV4FrameRange*>(ss.dev + off_frames)}, st);
+    } else if (with_envs) {
         const PtV4Envs ea{envs->table, envs->count, reinterpret_cast<const int32_t*>(ss.dev + off_emap)};
         e = pt_launch_v4_envs(j, va, sa, ea, st);
     } else {
         e = pt_launch_v4_scenes(j, va, sa, st);
     }
-    if (e != hipSuccess) return fail(PT_EHIP, "v4 %s launch failed: %s", with_envs ? "envs" : "scenes", hipGetErrorString(e));
+    if (e != hipSuccess)
+        return fail(PT_EHIP, "v4 %s launch failed: %s", batch ? "batch" : with_envs ? "envs" : "scenes", hipGetErrorString(e));
     HIP_TRY(hipEventRecord(ss.done, st));
     ss.pending = true;
     if ((rc = queue_done(dv, ls.slot, st, true))) return rc;
@@ -2984,14 +3042,41 @@ static int v4_scenes_launch(const pt_device_job* dj, bool with_envs, const pt_v4
 int pt_v4_render_device_scenes(const pt_device_job* dj, const pt_v4_scene_desc* scenes, int32_t nscenes, const pt_v4_camera* cams,
                                const int32_t* scene_of_view, int32_t nviews, uint32_t* pixels, int32_t format, void* stream)
 {
-    return v4_scenes_launch(dj, false, nullptr, nullptr, scenes, nscenes, scene_of_view, cams, nviews, pixels, format, stream);
+    pt_v4_batch a{};
+    a.cams = cams;
+    a.nviews = nviews;
+    a.scenes = scenes;
+    a.nscenes = nscenes;
+    a.scene_of_view = scene_of_view;
+    a.pixels = pixels;
+    a.format = format;
+    return v4_scenes_launch(dj, V4BatchKind::kScenes, a, stream);
 }
 
 int pt_v4_render_device_envs(const pt_device_job* dj, const pt_v4_env_set* envs, const int32_t* env_of_view,
                              const pt_v4_scene_desc* scenes, int32_t nscenes, const int32_t* scene_of_view, const pt_v4_camera* cams,
                              int32_t nviews, uint32_t* pixels, int32_t format, void* stream)
 {
-    return v4_scenes_launch(dj, true, envs, env_of_view, scenes, nscenes, scene_of_view, cams, nviews, pixels, format, stream);
+    pt_v4_batch a{};
+    a.cams = cams;
+    a.nviews = nviews;
+    a.scenes = scenes;
+    a.nscenes = nscenes;
+    a.scene_of_view = scene_of_view;
+    a.envs = envs;
+    a.env_of_view = env_of_view;
+    a.pixels = pixels;
+    a.format = format;
+    return v4_scenes_launch(dj, V4BatchKind::kEnvs, a, stream);
+}
+
+static_assert(sizeof(pt_v4_frame_range) == sizeof(PtV4FrameRange) && offsetof(pt_v4_frame_range, nframes) == offsetof(PtV4FrameRange, nframes),
+              "pt_v4_frame_range is PtV4FrameRange");
+
+int pt_v4_render_device_batch(const pt_device_job* dj, const pt_v4_batch* b, void* stream)
+{
+    if (!b) return fail(PT_EINVAL, "null batch");
+    return v4_scenes_launch(dj, V4BatchKind::kBatch, *b, stream);
 }
 
 int pt_v4_count_device(const pt_device_job* dj, void* stream, pt_work_counts* out)

@@ -113,6 +113,8 @@ enum PtGuardId : uint32_t {
                             // scene record whose object counts exceed PT_V4_MAX_OBJECTS
     PT_G_ENV = 18,          // an envs launch: a view's env index beyond the env set, or (value | 2^31) an env
                             // record whose width or height is not positive
+    PT_G_FRAMES = 19,       // a batch launch: a view's frame range record with nframes < 0, frame_first < 1 or
+                            // frame_first + nframes beyond 2^24; value: the view
 };
 
 // Tile queues: one counter per XCD group, 128 B apart (PT_QUEUE_WORDS u32 per launch).

@@ -301,3 +301,24 @@ constexpr PtKeyList<PtV4EnvsKey, kPtV4EnvsKeyCount> pt_v4_envs_key_list()
     return l;
 }
 constexpr PtKeyList<PtV4EnvsKey, kPtV4EnvsKeyCount> kPtV4EnvsKeys = pt_v4_envs_key_list();
+
+// ---- v4 batch (pt_v4.hip pt_v4_batch_kernel <env, layout, fexp>) ----
+// The superset launch (a camera, a scene, an env map and a frame range per view) has an instance for every
+// env term, none included: 12 keys, in a list of its own.
+struct PtV4BatchKey {
+    int env, layout, fexp;
+    constexpr bool operator==(const PtV4BatchKey& o) const { return env == o.env && layout == o.layout && fexp == o.fexp; }
+};
+constexpr bool pt_pick_v4_batch_valid(int env, int layout) { return env >= 0 && env < 3 && layout >= 0 && layout < kPickTiled; }
+constexpr PtV4BatchKey pt_pick_v4_batch_key(int env, int layout, bool fast_exp) { return {env, layout, fast_exp ? 1 : 0}; }
+constexpr size_t kPtV4BatchKeyCount = 3 * 2 * 2;
+constexpr PtKeyList<PtV4BatchKey, kPtV4BatchKeyCount> pt_v4_batch_key_list()
+{
+    PtKeyList<PtV4BatchKey, kPtV4BatchKeyCount> l{};
+    size_t n = 0;
+    for (int env = 0; env < 3; ++env)
+        for (int layout = 0; layout < kPickTiled; ++layout)
+            for (int fexp = 1; fexp >= 0; --fexp) l.k[n++] = {env, layout, fexp};
+    return l;
+}
+constexpr PtKeyList<PtV4BatchKey, kPtV4BatchKeyCount> kPtV4BatchKeys = pt_v4_batch_key_list();

@@ -193,3 +193,25 @@ struct PtV4Envs {
 // of pt_v4_envs_kernel.  job.env_mode is not NONE; job.env, env_w and env_h are not read.
 hipError_t pt_launch_v4_envs(const PtV4Job& job, const PtV4Views& views, const PtV4Scenes& scenes, const PtV4Envs& envs,
                              hipStream_t stream);
+
+// ---- a batch with a frame range per view (pt_v4_render_device_batch; pt_v4.hip pt_v4_batch_kernel) ----
+// The superset of the three launches above: a view is (camera, scene, environment, frame range).  View v
+// renders frames [frame_first, frame_first + nframes) of its own -- a parallel array of 8-byte records,
+// like scene_of_view and env_of_view (PtV4View stays as it is).  A wave reads its view's record when it
+// takes a tile: one 8-byte read through the constant address space at a wave-uniform address, so first
+// frame and count change together and live in scalar registers.  job.frame_first and job.nframes are not
+// read.  A view of 0 frames keeps its accumulator (loaded, not stored) and still packs its pixels.
+// With an env term (job.env_mode not NONE) the texture is always a record of `envs`, as in an envs launch
+// (the host stages a one-record table for pt_set_env_map's texture); without one `envs` is not read.
+struct PtV4FrameRange {
+    uint32_t frame_first;   // iFrame of the view's first frame (>= 1)
+    int32_t nframes;        // >= 0; frame_first + nframes <= 2^24
+};
+static_assert(sizeof(PtV4FrameRange) == 8, "a frame range record is 8 B");
+struct PtV4Frames {
+    const PtV4FrameRange* range_of_view;   // device memory, one record per view
+};
+// pt_launch_v4_envs with the range per view: the instances (ENV x row layout x FEXP, 12) of
+// pt_v4_batch_kernel.  The caller launches only when some view has frames.
+hipError_t pt_launch_v4_batch(const PtV4Job& job, const PtV4Views& views, const PtV4Scenes& scenes, const PtV4Envs& envs,
+                              const PtV4Frames& frames, hipStream_t stream);

@@ -932,7 +932,8 @@ __device__ __forceinline__ void v4_present(const PtV4Job& job, int X, int Y, V3 
 template <int ENV, int LAYOUT, bool COUNT, bool DEF, int FEXP, bool DFL = false, bool PRESENT = false>
 __global__ __launch_bounds__(64 * kWaves) PT_V4_OCC void pt_v4_kernel(PtV4Job job, PtV4Scene sc)
 {
-    constexpr bool VIEWS = false, SCENES = false, ENVS = false;
+    constexpr bool VIEWS = false, SCENES = false, ENVS = false, FRAMES = false;
+    constexpr PtV4Frames fa{nullptr};                  // (named in discarded statements only)
     constexpr PtV4Views va{nullptr, 0, nullptr, 0u};   // (named in discarded statements only)
     constexpr PtV4Scenes sa{nullptr, 0, nullptr};      // (likewise)
     constexpr PtV4Envs ea{nullptr, 0, nullptr};        // (likewise)
@@ -949,7 +950,8 @@ template <int ENV, int LAYOUT, int FEXP>
 __global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_views_kernel(PtV4Job job, PtV4Scene sc, PtV4Views va)
 {
     static_assert(LAYOUT != PT_LAYOUT_TILED_PLANAR8, "views run the generic, uncounted row-layout form");
-    constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = false, ENVS = false;
+    constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = false, ENVS = false, FRAMES = false;
+    constexpr PtV4Frames fa{nullptr};               // (named in discarded statements only)
     constexpr PtV4Scenes sa{nullptr, 0, nullptr};   // (named in discarded statements only)
     constexpr PtV4Envs ea{nullptr, 0, nullptr};     // (likewise)
     V4SceneRec srec;                                // (likewise)
@@ -965,7 +967,8 @@ template <int ENV, int LAYOUT, int FEXP>
 __global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_scenes_kernel(PtV4Job job, PtV4Views va, PtV4Scenes sa)
 {
     static_assert(LAYOUT != PT_LAYOUT_TILED_PLANAR8, "scenes run the generic, uncounted row-layout form");
-    constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = true, ENVS = false;
+    constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = true, ENVS = false, FRAMES = false;
+    constexpr PtV4Frames fa{nullptr};             // (named in discarded statements only)
     constexpr PtV4Scene sc{};   // (named in discarded statements only)
     constexpr PtV4Envs ea{nullptr, 0, nullptr};   // (likewise)
     V4ViewCam cam;      // the tile's view's camera
@@ -983,10 +986,29 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_envs_kernel
 {
     static_assert(LAYOUT != PT_LAYOUT_TILED_PLANAR8, "envs run the generic, uncounted row-layout form");
     static_assert(ENV != PT_V4_ENV_NONE_, "an envs launch has an env term");
-    constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = true, ENVS = true;
+    constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = true, ENVS = true, FRAMES = false;
     constexpr PtV4Scene sc{};   // (named in discarded statements only)
+    constexpr PtV4Frames fa{nullptr};   // (likewise)
     V4ViewCam cam;      // the tile's view's camera,
     V4SceneRec srec;    // its scene and (the pool's `tex`) its texture: all taken when the wave takes a tile
+#include "pt_v4_tile_pool.inc"
+}
+
+// A batch with a frame range per view (pt_v4_render_device_batch, pt_v4.h PtV4Frames): the scenes kernel's
+// text with ENVS wherever there is an env term and the view's own (frame_first, nframes) -- ENV none /
+// equirect / cubemap x row layout x FEXP, 12 instances (pt_kernel_pick.h kPtV4BatchKeys).  Everything it
+// adds to the pool's body sits under FRAMES.  Nothing of the range is block-shared: the four waves of a
+// block may be on four ranges at once.
+template <int ENV, int LAYOUT, int FEXP>
+__global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_batch_kernel(PtV4Job job, PtV4Views va, PtV4Scenes sa, PtV4Envs ea,
+                                                                                  PtV4Frames fa)
+{
+    static_assert(LAYOUT != PT_LAYOUT_TILED_PLANAR8, "batches run the generic, uncounted row-layout form");
+    constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = true;
+    constexpr bool ENVS = ENV != PT_V4_ENV_NONE_, FRAMES = true;
+    constexpr PtV4Scene sc{};   // (named in discarded statements only)
+    V4ViewCam cam;      // the tile's view's camera,
+    V4SceneRec srec;    // its scene, its texture (the pool's `tex`) and its frame range: all taken with the tile
 #include "pt_v4_tile_pool.inc"
 }
 
@@ -1548,6 +1570,21 @@ constexpr PtKeyList<V4EnvsInstance, sizeof...(I)> v4_envs_table(std::index_seque
 constexpr auto kV4EnvsTable = v4_envs_table(std::make_index_sequence<kPtV4EnvsKeyCount>{});
 PtResidentCache<kPtV4EnvsKeyCount> v4_envs_resident;
 
+// The batch instances: entry i is the kernel of kPtV4BatchKeys[i], as above.
+using V4BatchKernel = void (*)(PtV4Job, PtV4Views, PtV4Scenes, PtV4Envs, PtV4Frames);
+struct V4BatchInstance {
+    PtV4BatchKey key;
+    V4BatchKernel kern;
+};
+template <size_t... I>
+constexpr PtKeyList<V4BatchInstance, sizeof...(I)> v4_batch_table(std::index_sequence<I...>)
+{
+    constexpr auto& k = kPtV4BatchKeys.k;
+    return {{V4BatchInstance{k[I], pt_v4_batch_kernel<k[I].env, k[I].layout, k[I].fexp>}...}};
+}
+constexpr auto kV4BatchTable = v4_batch_table(std::make_index_sequence<kPtV4BatchKeyCount>{});
+PtResidentCache<kPtV4BatchKeyCount> v4_batch_resident;
+
 }  // namespace
 
 hipError_t pt_v4_set_chain_polls(uint32_t polls)
@@ -1662,5 +1699,30 @@ hipError_t pt_launch_v4_envs(const PtV4Job& j, const PtV4Views& va, const PtV4Sc
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kV4EnvsTable.k[i].kern, dim3(grid), dim3(64 * kWaves), 0, st, j, va, sa, ea);
+    return hipGetLastError();
+}
+
+hipError_t pt_launch_v4_batch(const PtV4Job& j, const PtV4Views& va, const PtV4Scenes& sa, const PtV4Envs& ea, const PtV4Frames& fa,
+                              hipStream_t st)
+{
+    if (j.ncols <= 0 || j.nrows <= 0) return hipSuccess;   // (job.nframes is not read: the caller knows that some view has frames)
+    if (!va.table || va.nviews < 1 || j.col0 != 0 || j.ncols != j.width) return hipErrorInvalidValue;
+    if (!sa.table || sa.nscenes < 1 || !sa.scene_of_view || !fa.range_of_view) return hipErrorInvalidValue;
+    if (j.env_mode != PT_V4_ENV_NONE_ && (!ea.table || ea.nenvs < 1 || !ea.env_of_view)) return hipErrorInvalidValue;
+    if (!j.queue || j.order || j.units || j.cost || j.counters) return hipErrorInvalidValue;   // unscheduled, uncounted
+    if (!pt_pick_v4_batch_valid(j.env_mode, j.layout)) return hipErrorInvalidValue;
+    const uint64_t tiles = (uint64_t)((j.ncols + 7) / 8) * (uint64_t)((j.nrows + 7) / 8) * (uint64_t)va.nviews;
+    if (tiles > PT_TILE_MASK) return hipErrorInvalidValue;   // (a queue entry carries view * tiles + tile)
+    const int i = kPtV4BatchKeys.find(pt_pick_v4_batch_key(j.env_mode, j.layout, j.fast_exp != 0));
+    const int r = i < 0 ? 0 : v4_batch_resident.get((size_t)i, (const void*)kV4BatchTable.k[i].kern, 64 * kWaves);
+    if (r <= 0) return i < 0 ? hipErrorInvalidValue : hipErrorInvalidDevice;
+    uint32_t grid = pt_pick_grid((uint32_t)r, (uint32_t)tiles, kWaves);
+    if (va.grid_cap && grid > va.grid_cap) grid = va.grid_cap;
+    // the records' material constants first, as pt_launch_v4_scenes
+    const uint32_t rows = (uint32_t)sa.nscenes * PT_V4_MAX_OBJECTS;
+    hipLaunchKernelGGL(pt_v4_scenes_prep_kernel, dim3((rows + 255u) / 256u), dim3(256), 0, st, sa.table, sa.nscenes);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kV4BatchTable.k[i].kern, dim3(grid), dim3(64 * kWaves), 0, st, j, va, sa, ea, fa);
     return hipGetLastError();
 }

@@ -1,7 +1,8 @@
 // pt_v4_tile_pool.inc -- the body of the v4 per-tile pool kernels (pt_v4.hip includes it inside
-// pt_v4_kernel, pt_v4_views_kernel, pt_v4_scenes_kernel and pt_v4_envs_kernel, which declare ENV, LAYOUT,
-// COUNT, DEF, FEXP, DFL, PRESENT, VIEWS, SCENES, ENVS, the kernel arguments job and sc, `cam`, the views
-// arguments `va`, the scenes arguments `sa`, the view's scene `srec` and the envs arguments `ea`).
+// pt_v4_kernel, pt_v4_views_kernel, pt_v4_scenes_kernel, pt_v4_envs_kernel and pt_v4_batch_kernel, which
+// declare ENV, LAYOUT, COUNT, DEF, FEXP, DFL, PRESENT, VIEWS, SCENES, ENVS, FRAMES, the kernel arguments job
+// and sc, `cam`, the views arguments `va`, the scenes arguments `sa`, the view's scene `srec`, the envs
+// arguments `ea` and the frame ranges `fa`).
     // SCENES: no block-wide material table (each wave follows its own view's scene: srec.mat / srec.mx).
     // SLDS (the A/B build PT_V4_SCENES_LDS=1): a table per wave in LDS, refilled when the wave takes a tile,
     // paid for by a shorter env miss queue, so that the block stays within 25 LDS granules.
@@ -101,6 +102,27 @@
         tex = Tex{er->data, er->w, er->h};
         if (!PT_GUARD(job.err, tex.w > 0 && tex.h > 0, PT_G_ENV, 0x80000000u | env)) tex.w = tex.h = 1;
     }
+    // The tile's frame range: everything below that depends on the first frame or the frame count -- the
+    // chunk loop and nf, the seed, the blend factor and BOTH tq.next conditions -- reads these two and
+    // nothing else, so loop and queue cannot disagree about the count (exactly one tq.next per tile: in
+    // the chunk with c0 < t_nframes <= c0 + kChunk, or after the loop when t_nframes <= 0).
+    // (Without FRAMES they are the job's members, named where they are read -- `FRAMES ? view's : job's`
+    // with a constant condition is the job's member itself -- so the other kernels keep their instructions.)
+    uint32_t t_first = 0;
+    int t_nframes = 0;
+    if constexpr (FRAMES) {
+        // the view's own range (a wave goes from a view of 9 frames to one of 1, of 0, of 17): ONE 8-byte
+        // read through the constant address space at a wave-uniform address, so first frame and count are
+        // of the same record (a stale first frame with a fresh count would render the right number of
+        // frames from the wrong seeds) and both sit in scalar registers.  Nothing of it is block-shared.
+        const uint64_t fr = *(const __attribute__((address_space(4))) uint64_t*)(fa.range_of_view + view);
+        t_first = (uint32_t)fr;
+        t_nframes = (int)(uint32_t)(fr >> 32);
+        // (checked build: a bad record is reported and the view treated as one of 0 frames)
+        if (!PT_GUARD(job.err, t_nframes >= 0 && t_first >= 1u && (uint64_t)t_first + (uint64_t)(uint32_t)t_nframes <= (1ull << 24),
+                      PT_G_FRAMES, view))
+            t_nframes = 0;
+    }
     const int tcol = (vtile % tiles_x) * 8, trow = (vtile / tiles_x) * 8;
     uint32_t tile_work = 1;   // pool iterations of this tile (the schedule's cost)
 
@@ -117,11 +139,12 @@
             if (!PT_GUARD(job.err, pi + 2 * cs < pixel_extent<LAYOUT>(job), PT_G_PIXEL, pi)) pi = 0;
         if constexpr (VIEWS) pi += (size_t)view * (size_t)job.nrows * (size_t)job.width * 3u;
         acc_p = job.buf + pi;
-        if (job.accumulate) acc = v3(acc_p[0], acc_p[cs], acc_p[2 * cs]);   // (:1233: only to blend)
+        // (a view of 0 frames: its accumulator is read, to pack its pixel, and never written)
+        if (job.accumulate || (FRAMES && t_nframes <= 0)) acc = v3(acc_p[0], acc_p[cs], acc_p[2 * cs]);   // (:1233: only to blend; 0 frames: to pack)
     }
 
-    for (int c0 = 0; c0 < job.nframes; c0 += kChunk) {
-        const int nf = std::min(kChunk, job.nframes - c0);
+    for (int c0 = 0; c0 < (FRAMES ? t_nframes : job.nframes); c0 += kChunk) {
+        const int nf = std::min(kChunk, (FRAMES ? t_nframes : job.nframes) - c0);
         const int total = 64 * nf;
         int next = 0;      // wave-uniform
         int item = -1;     // this lane's (pixel, frame) sample, -1 = none
@@ -164,7 +187,7 @@
                         item = f * 64 + p;   // colour slot order (phase C)
                         // mainImage :1092-1130
                         const int Y = job.row_start + rb * job.row_stride;
-                        const uint32_t frame = job.frame_first + (uint32_t)(c0 + f);
+                        const uint32_t frame = (FRAMES ? t_first : job.frame_first) + (uint32_t)(c0 + f);
                         const int fyi = job.height - 1 - Y;
                         // 24 x 24-bit products: X, fyi, frame < 2^24 (C ABI), low words = the u32 products
                         rng = 1u | (__umul24((uint32_t)X, 1973u) + __umul24((uint32_t)fyi, 9277u) + __umul24(frame, 26699u));
@@ -259,7 +282,7 @@
             }
         }
         if (DEFER && qn > 0) drain(qn);
-        if (c0 + kChunk >= job.nframes) next_tile = tq.next(job.err);   // the last pool is done
+        if (c0 + kChunk >= (FRAMES ? t_nframes : job.nframes)) next_tile = tq.next(job.err);   // the last pool is done
         // all radiance of this chunk is in LDS (written by lanes of this wave)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -268,7 +291,7 @@
             for (int f = 0; f < nf; ++f) {
                 const float* c = col + (f * 64 + lane) * 3;
                 if (job.accumulate) {   // ACCUMULATE_FRAMES 1: fmadd(blend_factor, color - last, last) :1233-1241
-                    const float bf = rcp((float)(job.frame_first + (uint32_t)(c0 + f)) + 1.0f);   // :1200
+                    const float bf = rcp((float)((FRAMES ? t_first : job.frame_first) + (uint32_t)(c0 + f)) + 1.0f);   // :1200
                     acc = v3(fma_(bf, c[0] - acc.x, acc.x), fma_(bf, c[1] - acc.y, acc.y), fma_(bf, c[2] - acc.z, acc.z));
                 } else {                // ACCUMULATE_FRAMES 0: the frame's colour is stored (:1245-1250)
                     acc = v3(c[0], c[1], c[2]);
@@ -279,11 +302,13 @@
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
-    if (job.nframes <= 0) next_tile = tq.next(job.err);   // no chunk ran
+    if ((FRAMES ? t_nframes : job.nframes) <= 0) next_tile = tq.next(job.err);   // no chunk ran
     if (pvalid) {
-        acc_p[0] = acc.x;
-        acc_p[cs] = acc.y;
-        acc_p[2 * cs] = acc.z;
+        if (!FRAMES || t_nframes > 0) {
+            acc_p[0] = acc.x;
+            acc_p[cs] = acc.y;
+            acc_p[2 * cs] = acc.z;
+        }
         v4_present<PRESENT>(job, px, job.row_start + pr * job.row_stride, acc);
         if constexpr (VIEWS) {
             // the view's packed pixels, job rows (a device job: col0 0, ncols == width), when asked for

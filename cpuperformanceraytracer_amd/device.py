@@ -414,6 +414,64 @@ def render_v4_device_envs(buf, envs: V4EnvSet, cameras, width: int, height: int,
                                               _stream(stream)), "pt_v4_render_device_envs")
 
 
+def render_v4_device_batch(buf, cameras, width: int, height: int, *, frames=None, scenes=None, scene_of_view=None, envs=None,
+                           env_of_view=None, pixels=None, frame_first: int = 1, nframes: int = 0, num_bounces: int = 8,
+                           row_start: int = 0, row_stride: int = 1, nrows: int | None = None,
+                           layout: int = N.PT_LAYOUT_INTERLEAVED, use_env: bool | None = None,
+                           pixel_format: int = N.PT_PIXEL_RGBA8, stream=None) -> None:
+    """Everything per view in one launch (pt_v4_render_device_batch): render_v4_device_envs with a frame range
+    per view.  `frames` is a sequence of (frame_first, nframes), one per camera -- a view of 0 frames keeps its
+    slice of `buf` bit for bit and still gets its pixels -- or None: every view renders the keywords
+    frame_first / nframes (which are not read otherwise).  `scenes` None: the current scene.  `envs` None: the
+    map of set_env_map when use_env (None: "when a set is given"), else the ambient.  Slice v of `buf` ends bit
+    for bit as that view's env map, scene, v4_camera(*cameras[v]) and render_v4_device over frames[v] would
+    leave it; no process-wide state is changed.  Asynchronous on `stream`."""
+    nrows = height if nrows is None else nrows
+    cams = [(tuple(float(x) for x in pos), float(fov)) for pos, fov in cameras]
+    nviews = len(cams)
+    if any(len(pos) != 3 for pos, _ in cams):
+        raise N.PtError(N.PT_EINVAL, "render_v4_device_batch", "a camera position has three components")
+    if not 1 <= nviews <= N.PT_V4_MAX_VIEWS:
+        raise N.PtError(N.PT_EINVAL, "render_v4_device_batch", f"{nviews} cameras outside [1, {N.PT_V4_MAX_VIEWS}]")
+    if use_env is None:
+        use_env = envs is not None
+    job = _job(buf, width, height, row_start, row_stride, nviews * nrows, frame_first, nframes, num_bounces, layout, use_env)
+    job.nrows = nrows
+    if pixels is not None:
+        _check_pixels(pixels, nviews * nrows * width, buf)
+    keep = [(N.PtV4Camera * nviews)(*[N.PtV4Camera((ctypes.c_float * 3)(*pos), fov) for pos, fov in cams])]
+
+    def per_view(m, what, ctype, conv):
+        if m is None:
+            return None
+        if len(m) != nviews:
+            raise N.PtError(N.PT_EINVAL, "render_v4_device_batch", f"{what} has {len(m)} entries for {nviews} views")
+        keep.append((ctype * nviews)(*[conv(x) for x in m]))
+        return keep[-1]
+    b = N.PtV4Batch()
+    b.cams, b.nviews = keep[0], nviews
+    farr = per_view(frames, "frames", N.PtV4FrameRange, lambda r: N.PtV4FrameRange(int(r[0]), int(r[1])))
+    if farr is not None:
+        b.frames = farr
+    if scenes is not None:
+        descs = [v4_scene_desc(s) for s in scenes]
+        if not descs:
+            raise N.PtError(N.PT_EINVAL, "render_v4_device_batch", "no scenes")
+        keep.append((N.PtV4SceneDesc * len(descs))(*descs))
+        b.scenes, b.nscenes = keep[-1], len(descs)
+    smap = per_view(scene_of_view, "scene_of_view", ctypes.c_int32, int)
+    if smap is not None:
+        b.scene_of_view = smap
+    if envs is not None:
+        b.envs = envs.handle
+    emap = per_view(env_of_view, "env_of_view", ctypes.c_int32, int)
+    if emap is not None:
+        b.env_of_view = emap
+    b.pixels = pixels.data_ptr() if pixels is not None else None
+    b.format = pixel_format
+    N.check(N.load().pt_v4_render_device_batch(ctypes.byref(job), ctypes.byref(b), _stream(stream)), "pt_v4_render_device_batch")
+
+
 def count_v4_device(buf, width: int, height: int, *, frame_first: int, nframes: int, num_bounces: int = 8,
                     row_start: int = 0, row_stride: int = 1, nrows: int | None = None,
                     layout: int = N.PT_LAYOUT_INTERLEAVED, use_env: bool = False, stream=None) -> dict:

@@ -429,6 +429,48 @@ int pt_v4_render_device_envs(const pt_device_job* job, const pt_v4_env_set* envs
                              const pt_v4_scene_desc* scenes, int32_t nscenes, const int32_t* scene_of_view,
                              const pt_v4_camera* cams, int32_t nviews, uint32_t* pixels, int32_t format,
                              void* hip_stream);
+/* One BATCH call that takes everything per view: a view is (camera, scene, environment, frame range).
+ * It is the superset of the three calls above -- which stay exactly as they are -- with one thing more:
+ * view v renders frames [frames[v].frame_first, +frames[v].nframes) of its own.  The blend factor is
+ * 1 / (frame + 1) and the per-pixel seed is (X, Y, frame), so a view's frame number is its accumulation
+ * state: one launch can restart one viewport while the others continue, give every sample of a dataset
+ * its own noise pattern, and stop converged views while hard ones take more frames.
+ *   frames  NULL: every view uses job->frame_first / nframes.  Otherwise job->frame_first / nframes are
+ *           not read, and each range must be one pt_v4_render_device accepts: frame_first >= 1,
+ *           nframes >= 0, frame_first + nframes <= 2^24 (PT_EINVAL, pt_last_error names the view).
+ *   scenes  NULL: every view renders the current process-wide scene (nscenes must be 0, scene_of_view
+ *           NULL); otherwise as pt_v4_render_device_scenes.
+ *   envs    NULL with job->use_env and an env mode other than PT_V4_ENV_NONE: every view reads
+ *           pt_set_env_map's texture (PT_ESTATE without one); env_of_view must be NULL.  NULL without an
+ *           env term: the ambient.  Not NULL: as pt_v4_render_device_envs, which needs an env term.
+ *   result  view v's slice (the layout and offsets of the views call) is bit for bit what pt_set_env_map
+ *           (or the ambient), the view's scene through pt_v4_clear_scene + pt_v4_add_*,
+ *           pt_v4_set_camera(&cams[v]) and pt_v4_render_device with that view's range leave, under both
+ *           values of pt_v4_config.accumulate_frames.  A view of 0 frames keeps its accumulator slice bit
+ *           for bit (also with accumulate_frames 0), and its pixel slice is the packed value of that
+ *           accumulator: each pixel slice equals pt_tonemap_device of its accumulator slice, for every view.
+ *   If every view has 0 frames, or nrows == 0: PT_OK, no launch (and no pixels written).
+ * Checked before any GPU work -- PT_EINVAL: a NULL batch, everything the envs and scenes calls reject, a
+ * bad range, scenes NULL with nscenes != 0 or scene_of_view, envs NULL with env_of_view, envs without an
+ * env term.  As the other three: at most 2^30 - 1 (views x tiles), asynchronous, a plain launch (it ends a
+ * live chain), no process-wide state changed, no chained or counting form. */
+typedef struct pt_v4_frame_range {
+    uint32_t frame_first;
+    int32_t nframes;
+} pt_v4_frame_range;
+typedef struct pt_v4_batch {
+    const pt_v4_camera* cams;
+    int32_t nviews;
+    const pt_v4_frame_range* frames;      /* NULL: every view uses job->frame_first / nframes */
+    const pt_v4_scene_desc* scenes;       /* NULL: the current scene */
+    int32_t nscenes;
+    const int32_t* scene_of_view;
+    const pt_v4_env_set* envs;            /* NULL: pt_set_env_map's texture (when use_env) */
+    const int32_t* env_of_view;
+    uint32_t* pixels;
+    int32_t format;
+} pt_v4_batch;
+int pt_v4_render_device_batch(const pt_device_job* job, const pt_v4_batch* batch, void* hip_stream);
 int pt_v4_count_device(const pt_device_job* job, void* hip_stream, pt_work_counts* out);   /* sync */
 
 /* --- tile work queue: the host tile scheduler, on the GPU ------------------------
