@@ -89,7 +89,7 @@ struct Sched {
 constexpr int kSchedSlots = 16;
 constexpr int kBands = 4;   // PT_FLAG_PIN_HOST: row bands of a pipelined frame
 constexpr unsigned kQueueRing = 256;       // tile-queue ring slots (reuse across streams is event-ordered)
-constexpr unsigned kViewRing = 4;          // view tables of pt_v4_render_device_views (Dev::views)
+constexpr unsigned kViewRing = 4;          // staging blocks of the batched v4 launches (Dev::batch)
 // launches per schedule build (g.sched_rebuild; PT_MI355_SCHED_REBUILD): 256 -- a build restarts the
 // chained overlap and costs a one-workgroup kernel (~57 us at 1080p); 3-round A/B of chained steps vs 64
 // (profiles/r06/r06zl_*): c2 0.2160 vs 0.2189 ms, c4 0.4582 vs 0.4633, v4 0.3286 vs 0.3313
@@ -136,32 +136,24 @@ struct Dev {
     size_t dgather_cap = 0;
     hipEvent_t ev_gather = nullptr;     // recorded after this device's rows were stored
     bool peer_root = false;             // this device may store into the root's memory
-    // views launches (pt_v4_render_device_views): a ring of kViewRing view tables.  A launch fills the
-    // next slot's page-locked host table, copies it to the slot's device table on its stream and records
-    // the slot's event after its kernel; a slot is reused only once that event has completed (the host
-    // waits for it -- four launches back, normally long done).  So a table that an earlier asynchronous
-    // launch may still be reading, on this stream or another, is never written, and no stream is made
-    // to wait for another.
-    struct ViewSlot {
-        PtV4View* host = nullptr;       // PT_V4_MAX_VIEWS records, page-locked
-        PtV4View* dev = nullptr;
-        hipEvent_t done = nullptr;
-        bool pending = false;           // done has been recorded
-    } views[kViewRing];
-    unsigned views_next = 0;
-    // scenes launches (pt_v4_render_device_scenes): the same ring rule for one block per slot that holds
-    // the launch's scene records, its view table, its view -> scene mapping and (an envs launch,
-    // pt_v4_render_device_envs) its view -> texture mapping, in that order.  A block
-    // has the size its largest launch so far needed (a record is ~2 KiB: 1024 of them ~2 MiB), grown
-    // only after the slot's event completed.
-    struct SceneSlot {
+    // batched v4 launches (pt_v4_render_device_views / _scenes / _envs / _batch): a ring of kViewRing blocks
+    // shared by the four calls.  A launch fills the next slot's page-locked host block, copies it to the
+    // slot's device block on its stream and records the slot's event after its kernel; a slot is reused
+    // only once that event has completed (the host waits for it -- four launches back, normally long
+    // done).  So a block that an earlier asynchronous launch may still be reading, on this stream or
+    // another, is never written, and no stream is made to wait for another.  The block holds what the
+    // launch's kind needs, in this order: its scene records, its view table, its view -> scene mapping,
+    // its view -> texture mapping, a one-record env table, its frame ranges (a views launch: the view
+    // table alone).  A block has the size its largest launch so far needed (a scene record is ~2 KiB:
+    // 1024 of them ~2 MiB), grown only after the slot's event completed.
+    struct BatchSlot {
         unsigned char* host = nullptr;  // page-locked
         unsigned char* dev = nullptr;
         size_t cap = 0;                 // bytes of each
         hipEvent_t done = nullptr;
-        bool pending = false;
-    } scenes[kViewRing];
-    unsigned scenes_next = 0;
+        bool pending = false;           // done has been recorded
+    } batch[kViewRing];
+    unsigned batch_next = 0;
     // chained launches (pt_render_device_chain, launch_chain): consecutive launches of one geometry
     // alternate on two streams of the library's and overlap on the GPU
     struct Chain {
@@ -1654,14 +1646,8 @@ void free_dev(Dev& dv)
     if (dv.dtone_out) (void)hipFree(dv.dtone_out);
     if (dv.dgather) (void)hipFree(dv.dgather);
     if (dv.ev_gather) (void)hipEventDestroy(dv.ev_gather);
-    for (Dev::ViewSlot& v : dv.views) {
-        if (v.pending) (void)hipEventSynchronize(v.done);   // (its launch may run on a caller's stream)
-        if (v.done) (void)hipEventDestroy(v.done);
-        if (v.dev) (void)hipFree(v.dev);
-        if (v.host) (void)hipHostFree(v.host);
-    }
-    for (Dev::SceneSlot& s : dv.scenes) {
-        if (s.pending) (void)hipEventSynchronize(s.done);
+    for (Dev::BatchSlot& s : dv.batch) {
+        if (s.pending) (void)hipEventSynchronize(s.done);   // (its launch may run on a caller's stream)
         if (s.done) (void)hipEventDestroy(s.done);
         if (s.dev) (void)hipFree(s.dev);
         if (s.host) (void)hipHostFree(s.host);
@@ -2701,92 +2687,6 @@ int pt_v4_render_device_chain(const pt_device_job* dj, void* stream)
     return launch_chain(*dv, j, (hipStream_t)stream);
 }
 
-// A batch of views in one launch (include/pt_mi355.h; pt_v4.h PtV4Views).  Everything is checked before
-// the first HIP call.  The view table goes through the device's ring (Dev::views); the launch is a plain,
-// unscheduled one of the per-tile pool's views instances -- it joins (ends) a live chain and takes a
-// tile-queue ring slot like every plain launch, and touches no geometry's schedule state.
-int pt_v4_render_device_views(const pt_device_job* dj, const pt_v4_camera* cams, int32_t nviews, uint32_t* pixels,
-                              int32_t format, void* stream)
-{
-    int rc;
-    if (!dj) return fail(PT_EINVAL, "null device job");
-    {
-        pt_device_job geo = *dj;   // (the geometry / frame checks, as v4_device_job's)
-        geo.use_env = 0;
-        PtJob unused;
-        if ((rc = device_job(&geo, &unused))) return rc;
-    }
-    if (!cams) return fail(PT_EINVAL, "null camera array");
-    if (nviews < 1 || nviews > PT_V4_MAX_VIEWS) return fail(PT_EINVAL, "nviews %d outside [1, %d]", nviews, PT_V4_MAX_VIEWS);
-    if (pixels && format != PT_PIXEL_RGBA8 && format != PT_PIXEL_XRGB8) return fail(PT_EINVAL, "unknown pixel format %d", format);
-    const uint64_t view_tiles = (uint64_t)((dj->width + 7) / 8) * (uint64_t)((dj->nrows + 7) / 8);
-    if (view_tiles * (uint64_t)nviews > PT_TILE_MASK)
-        return fail(PT_EINVAL, "%d views x %llu tiles exceed the tile queue's %u entries", nviews, (unsigned long long)view_tiles,
-                    PT_TILE_MASK);
-    std::vector<float> dist((size_t)nviews);
-    for (int32_t v = 0; v < nviews; ++v)
-        if ((rc = v4_check_camera(&cams[v], &dist[(size_t)v], v))) return rc;
-    if (dj->nframes == 0 || dj->nrows == 0) return PT_OK;   // nothing to render
-
-    PtV4Job j;
-    Dev* dvp = nullptr;
-    DeviceGuard guard;
-    if ((rc = ensure_init()) || (rc = v4_device_job(dj, &j)) || (rc = dev_of(dj->buf, &dvp)) || (rc = use_dev(*dvp))) return rc;
-    Dev& dv = *dvp;
-    hipStream_t st = (hipStream_t)stream;
-    // the job's own camera fields are not read by the views instances
-    memset(j.cam_pos, 0, sizeof(j.cam_pos));
-    j.cam_dist = 0.0f;
-    j.sky = PtV4SkyWin{-1, {}};
-    j.default_scene = 0;
-    if (j.env_mode != PT_V4_ENV_NONE) j.env = dv.denv;
-    j.err = dv.derr;
-    // the render kernel writes the pixels with the default tonemap pair; any other pair: a second pass
-    const bool fused = pixels && g.v4cfg.fast_aces && g.v4cfg.fast_gamma;
-    j.pix_xrgb = format == PT_PIXEL_XRGB8;
-
-    Dev::ViewSlot& vs = dv.views[dv.views_next++ % kViewRing];
-    const size_t table_bytes = (size_t)PT_V4_MAX_VIEWS * sizeof(PtV4View);
-    if (!vs.host && hipHostMalloc(&vs.host, table_bytes, hipHostMallocDefault) != hipSuccess) {
-        vs.host = nullptr;
-        return fail(PT_ENOMEM, "hipHostMalloc(view table) failed");
-    }
-    if (!vs.dev && hipMalloc(&vs.dev, table_bytes) != hipSuccess) {
-        vs.dev = nullptr;
-        return fail(PT_ENOMEM, "hipMalloc(view table) failed");
-    }
-    if (!vs.done) HIP_TRY(hipEventCreateWithFlags(&vs.done, hipEventDisableTiming));
-    if (vs.pending) {   // the slot's previous launch (kViewRing launches back) still reads the table: wait for it
-        HIP_TRY(hipEventSynchronize(vs.done));
-        vs.pending = false;
-    }
-    for (int32_t v = 0; v < nviews; ++v) {
-        PtV4View& r = vs.host[v];
-        memcpy(r.cam_pos, cams[v].position, sizeof(r.cam_pos));
-        r.cam_dist = dist[(size_t)v];
-        v4_sky_window_of(cams[v].position, &r.sky);
-    }
-    HIP_TRY(hipMemcpyAsync(vs.dev, vs.host, (size_t)nviews * sizeof(PtV4View), hipMemcpyHostToDevice, st));
-
-    LaunchSched ls;
-    if ((rc = chain_join(dv, st)) || (rc = use_queue_slot(dv, st, &ls))) return rc;
-    j.queue = ls.queue;
-    j.queue_next = ls.queue_next;
-    const PtV4Views va{vs.dev, nviews, fused ? pixels : nullptr, g.v4_views_grid};
-    hipError_t e = pt_launch_v4_views(j, g.v4scene, va, st);
-    if (e != hipSuccess) return fail(PT_EHIP, "v4 views launch failed: %s", hipGetErrorString(e));
-    HIP_TRY(hipEventRecord(vs.done, st));
-    vs.pending = true;
-    if ((rc = queue_done(dv, ls.slot, st, true))) return rc;
-    if (pixels && !fused) {
-        // (the slices lie back to back: one image of nviews x nrows rows in either row layout)
-        const PtToneJob tj = tone_job(j.buf, j.ncols, j.nrows * nviews, j.layout, 0, 0, pixels, format);
-        e = pt_launch_tonemap(tj, st);
-        if (e != hipSuccess) return fail(PT_EHIP, "tonemap launch failed: %s", hipGetErrorString(e));
-    }
-    return PT_OK;
-}
-
 static_assert(sizeof(pt_v4_scene_desc) == sizeof(PtV4SceneDesc) && offsetof(pt_v4_scene_desc, quads) == offsetof(PtV4SceneDesc, quad) &&
               offsetof(pt_v4_scene_desc, spheres) == offsetof(PtV4SceneDesc, sphere) &&
               offsetof(pt_v4_scene_desc, materials) == offsetof(PtV4SceneDesc, mat) &&
@@ -2802,14 +2702,21 @@ int pt_v4_get_scene_desc(pt_v4_scene_desc* out)
     return PT_OK;
 }
 
-// A batch of scenes in one launch (include/pt_mi355.h; pt_v4.h PtV4Scenes): pt_v4_render_device_views with
-// the scene per view.  Everything is checked before the first HIP call; nothing of the process-wide scene,
-// camera or frame counter is read or written (the job is made from the arguments and the pt_v4_config
-// alone).  Each record is pt_v4_build_scene of its description -- the code behind pt_v4_add_* -- and each
-// view's window pt_v4_skywin_build of (its scene, its camera).  Records, view table and mapping travel in
-// one block of the device's scene ring (Dev::scenes).
-// The three public calls are one function: `kind` says which call it is, and the arguments travel as a
-// pt_v4_batch (the scenes and envs calls fill one; they leave `frames` NULL and never read it).
+// The batched v4 launches (include/pt_mi355.h; pt_v4.h PtV4Views ... PtV4Frames).  Everything is checked
+// before the first HIP call.  The launch is a plain, unscheduled one of the kind's instances
+// (pt_launch_v4_batched) -- it joins (ends) a live chain and takes a tile-queue ring slot like every plain
+// launch, and touches no geometry's schedule state.  What the kernel reads per view travels in one block of
+// the device's batch ring (Dev::batch).
+// The four public calls are one function: `kind` says which call it is, and the arguments travel as a
+// pt_v4_batch (the views, scenes and envs calls fill one; they leave `frames` NULL and never read it).
+//   kViews  (pt_v4_render_device_views): a camera per view.  Every view renders the current process-wide
+//           scene, a kernel argument (g.v4scene), with the window of (that scene, its camera); the block is
+//           the view table alone.
+//   kScenes (pt_v4_render_device_scenes): the scene per view as well.  Nothing of the process-wide scene,
+//           camera or frame counter is read or written (the job is made from the arguments and the
+//           pt_v4_config alone).  Each record is pt_v4_build_scene of its description -- the code behind
+//           pt_v4_add_* -- and each view's window pt_v4_skywin_build of (its scene, its camera).  Records,
+//           view table and mapping travel in the block.
 //   kEnvs   (pt_v4_render_device_envs): the texture per view as well -- view v reads record env_of_view[v]
 //           of the env set's device table; the mapping travels at the end of the same block.  Then `scenes`
 //           may be NULL: every view renders the current process-wide scene (the one thing of the
@@ -2820,11 +2727,11 @@ int pt_v4_get_scene_desc(pt_v4_scene_desc* out)
 //           view when `envs` is given; without a set but with an env term, the process-wide map travels as
 //           a one-record table in the block (with a mapping of zeros), so that the kernel reads a table
 //           either way.
-enum class V4BatchKind { kScenes, kEnvs, kBatch };
+using V4BatchKind = PtV4BatchKind;   // (pt_kernel_pick.h: kViews, kScenes, kEnvs, kBatch)
 
-static int v4_scenes_launch(const pt_device_job* dj, V4BatchKind kind, const pt_v4_batch& args, void* stream)
+static int v4_batched_launch(const pt_device_job* dj, V4BatchKind kind, const pt_v4_batch& args, void* stream)
 {
-    const bool batch = kind == V4BatchKind::kBatch;
+    const bool views = kind == V4BatchKind::kViews, batch = kind == V4BatchKind::kBatch;
     const bool with_envs = kind == V4BatchKind::kEnvs || (batch && args.envs);   // a texture per view, from an env set
     const pt_v4_camera* const cams = args.cams;
     const int32_t nviews = args.nviews;
@@ -2865,14 +2772,16 @@ static int v4_scenes_launch(const pt_device_job* dj, V4BatchKind kind, const pt_
         scenes = reinterpret_cast<const pt_v4_scene_desc*>(&g.v4desc);
         nscenes = 1;
     }
-    if (!scenes) return fail(PT_EINVAL, "null scene array");
-    if (nscenes < 1 || nscenes > PT_V4_MAX_VIEWS) return fail(PT_EINVAL, "nscenes %d outside [1, %d]", nscenes, PT_V4_MAX_VIEWS);
-    if (!scene_of_view && !current_scene && nscenes != nviews)
-        return fail(PT_EINVAL, "no scene_of_view: view v uses scene v, but nscenes %d != nviews %d", nscenes, nviews);
-    if (scene_of_view)
-        for (int32_t v = 0; v < nviews; ++v)
-            if (scene_of_view[v] < 0 || scene_of_view[v] >= nscenes)
-                return fail(PT_EINVAL, "view %d: scene_of_view %d outside [0, %d)", v, scene_of_view[v], nscenes);
+    if (!views) {   // (a views launch has no records: nscenes stays 0)
+        if (!scenes) return fail(PT_EINVAL, "null scene array");
+        if (nscenes < 1 || nscenes > PT_V4_MAX_VIEWS) return fail(PT_EINVAL, "nscenes %d outside [1, %d]", nscenes, PT_V4_MAX_VIEWS);
+        if (!scene_of_view && !current_scene && nscenes != nviews)
+            return fail(PT_EINVAL, "no scene_of_view: view v uses scene v, but nscenes %d != nviews %d", nscenes, nviews);
+        if (scene_of_view)
+            for (int32_t v = 0; v < nviews; ++v)
+                if (scene_of_view[v] < 0 || scene_of_view[v] >= nscenes)
+                    return fail(PT_EINVAL, "view %d: scene_of_view %d outside [0, %d)", v, scene_of_view[v], nscenes);
+    }
     const PtV4SceneDesc* const desc = reinterpret_cast<const PtV4SceneDesc*>(scenes);
     for (int32_t s = 0; s < nscenes; ++s) {
         const PtV4SceneDesc& d = desc[s];
@@ -2911,8 +2820,8 @@ static int v4_scenes_launch(const pt_device_job* dj, V4BatchKind kind, const pt_
 
     Dev* dvp = nullptr;
     DeviceGuard guard;
-    if ((rc = ensure_init())) return rc;
-    // the job of v4_device_job without the process-wide scene and camera: the arguments and the config
+    if ((rc = ensure_init()) || (views && (rc = v4_ensure_scene()))) return rc;
+    // the job of v4_device_job without the process-wide camera: the arguments and the config
     PtV4Job j{};
     j.buf = dj->buf;
     j.width = dj->width;
@@ -2955,12 +2864,12 @@ static int v4_scenes_launch(const pt_device_job* dj, V4BatchKind kind, const pt_
     const auto up16 = [](size_t n) { return (n + 15u) & ~(size_t)15u; };
     const size_t off_views = up16((size_t)nscenes * sizeof(PtV4SceneRec));
     const size_t off_map = off_views + up16((size_t)nviews * sizeof(PtV4View));
-    const size_t off_emap = off_map + up16((size_t)nviews * sizeof(int32_t));
+    const size_t off_emap = off_map + (views ? 0u : up16((size_t)nviews * sizeof(int32_t)));
     const bool staged_env = batch && !with_envs && j.env_mode != PT_V4_ENV_NONE;
     const size_t off_erec = off_emap + (with_envs || staged_env ? up16((size_t)nviews * sizeof(int32_t)) : 0u);
     const size_t off_frames = off_erec + (staged_env ? up16(sizeof(PtV4EnvRec)) : 0u);
     const size_t need = off_frames + (batch ? up16((size_t)nviews * sizeof(PtV4FrameRange)) : 0u);
-    Dev::SceneSlot& ss = dv.scenes[dv.scenes_next++ % kViewRing];
+    Dev::BatchSlot& ss = dv.batch[dv.batch_next++ % kViewRing];
     if (!ss.done) HIP_TRY(hipEventCreateWithFlags(&ss.done, hipEventDisableTiming));
     if (ss.pending) {   // the slot's previous launch (kViewRing launches back) still reads the block: wait for it
         HIP_TRY(hipEventSynchronize(ss.done));
@@ -2974,12 +2883,12 @@ static int v4_scenes_launch(const pt_device_job* dj, V4BatchKind kind, const pt_
         const size_t cap = (need + 4095u) & ~(size_t)4095u;
         if (hipHostMalloc((void**)&ss.host, cap, hipHostMallocDefault) != hipSuccess) {
             ss.host = nullptr;
-            return fail(PT_ENOMEM, "hipHostMalloc(scene table, %zu bytes) failed", cap);
+            return fail(PT_ENOMEM, "hipHostMalloc(batch block, %zu bytes) failed", cap);
         }
         if (hipMalloc((void**)&ss.dev, cap) != hipSuccess) {
             (void)hipHostFree(ss.host);
             ss.host = ss.dev = nullptr;
-            return fail(PT_ENOMEM, "hipMalloc(scene table, %zu bytes) failed", cap);
+            return fail(PT_ENOMEM, "hipMalloc(batch block, %zu bytes) failed", cap);
         }
         ss.cap = cap;
     }
@@ -2992,7 +2901,7 @@ static int v4_scenes_launch(const pt_device_job* dj, V4BatchKind kind, const pt_
     }
     for (int32_t v = 0; v < nviews; ++v) {
         const int32_t s = scene_of_view ? scene_of_view[v] : current_scene ? 0 : v;
-        hmap[v] = s;
+        if (!views) hmap[v] = s;
         if (with_envs) reinterpret_cast<int32_t*>(ss.host + off_emap)[v] = env_of_view ? env_of_view[v] : v;
         if (staged_env) reinterpret_cast<int32_t*>(ss.host + off_emap)[v] = 0;
         if (batch)
@@ -3001,7 +2910,7 @@ static int v4_scenes_launch(const pt_device_job* dj, V4BatchKind kind, const pt_
         PtV4View& r = hview[v];
         memcpy(r.cam_pos, cams[v].position, sizeof(r.cam_pos));
         r.cam_dist = dist[(size_t)v];
-        v4_sky_window_for(desc[s], cams[v].position, &r.sky);
+        v4_sky_window_for(views ? g.v4desc : desc[s], cams[v].position, &r.sky);
     }
     if (staged_env) *reinterpret_cast<PtV4EnvRec*>(ss.host + off_erec) = PtV4EnvRec{dv.denv, j.env_w, j.env_h};
     HIP_TRY(hipMemcpyAsync(ss.dev, ss.host, need, hipMemcpyHostToDevice, st));
@@ -3012,21 +2921,16 @@ static int v4_scenes_launch(const pt_device_job* dj, V4BatchKind kind, const pt_
     j.queue_next = ls.queue_next;
     const PtV4Views va{reinterpret_cast<const PtV4View*>(ss.dev + off_views), nviews, fused ? pixels : nullptr, g.v4_views_grid};
     const PtV4Scenes sa{reinterpret_cast<PtV4SceneRec*>(ss.dev), nscenes, reinterpret_cast<const int32_t*>(ss.dev + off_map)};
-    hipError_t e;
-    if (batch) {
-        const int32_t* const emap = reinterpret_cast<const int32_t*>(ss.dev + off_emap);
-        const PtV4Envs ea = with_envs    ? PtV4Envs{envs->table, envs->count, emap}
-                            : staged_env ? PtV4Envs{reinterpret_cast<const PtV4EnvRec*>(ss.dev + off_erec), 1, emap}
-                                         : PtV4Envs{nullptr, 0, nullptr};
-        e = pt_launch_v4_batch(j, va, sa, ea, PtV4Frames{reinterpret_cast<const PtV4FrameRange*>(ss.dev + off_frames)}, st);
-    } else if (with_envs) {
-        const PtV4Envs ea{envs->table, envs->count, reinterpret_cast<const int32_t*>(ss.dev + off_emap)};
-        e = pt_launch_v4_envs(j, va, sa, ea, st);
-    } else {
-        e = pt_launch_v4_scenes(j, va, sa, st);
-    }
+    const int32_t* const emap = reinterpret_cast<const int32_t*>(ss.dev + off_emap);
+    const PtV4Envs ea = with_envs    ? PtV4Envs{envs->table, envs->count, emap}
+                        : staged_env ? PtV4Envs{reinterpret_cast<const PtV4EnvRec*>(ss.dev + off_erec), 1, emap}
+                                     : PtV4Envs{nullptr, 0, nullptr};
+    const PtV4Frames fa{reinterpret_cast<const PtV4FrameRange*>(ss.dev + off_frames)};
+    // (what the kind does not read is not passed; a views launch renders the process-wide scene)
+    hipError_t e = pt_launch_v4_batched(kind, j, views ? &g.v4scene : nullptr, va, views ? nullptr : &sa, ea.table ? &ea : nullptr,
+                                        batch ? &fa : nullptr, st);
     if (e != hipSuccess)
-        return fail(PT_EHIP, "v4 %s launch failed: %s", batch ? "batch" : with_envs ? "envs" : "scenes", hipGetErrorString(e));
+        return fail(PT_EHIP, "v4 %s launch failed: %s", views ? "views" : batch ? "batch" : with_envs ? "envs" : "scenes", hipGetErrorString(e));
     HIP_TRY(hipEventRecord(ss.done, st));
     ss.pending = true;
     if ((rc = queue_done(dv, ls.slot, st, true))) return rc;
@@ -3037,6 +2941,17 @@ static int v4_scenes_launch(const pt_device_job* dj, V4BatchKind kind, const pt_
         if (e != hipSuccess) return fail(PT_EHIP, "tonemap launch failed: %s", hipGetErrorString(e));
     }
     return PT_OK;
+}
+
+int pt_v4_render_device_views(const pt_device_job* dj, const pt_v4_camera* cams, int32_t nviews, uint32_t* pixels,
+                              int32_t format, void* stream)
+{
+    pt_v4_batch a{};
+    a.cams = cams;
+    a.nviews = nviews;
+    a.pixels = pixels;
+    a.format = format;
+    return v4_batched_launch(dj, V4BatchKind::kViews, a, stream);
 }
 
 int pt_v4_render_device_scenes(const pt_device_job* dj, const pt_v4_scene_desc* scenes, int32_t nscenes, const pt_v4_camera* cams,
@@ -3050,7 +2965,7 @@ int pt_v4_render_device_scenes(const pt_device_job* dj, const pt_v4_scene_desc* 
     a.scene_of_view = scene_of_view;
     a.pixels = pixels;
     a.format = format;
-    return v4_scenes_launch(dj, V4BatchKind::kScenes, a, stream);
+    return v4_batched_launch(dj, V4BatchKind::kScenes, a, stream);
 }
 
 int pt_v4_render_device_envs(const pt_device_job* dj, const pt_v4_env_set* envs, const int32_t* env_of_view,
@@ -3067,7 +2982,7 @@ int pt_v4_render_device_envs(const pt_device_job* dj, const pt_v4_env_set* envs,
     a.env_of_view = env_of_view;
     a.pixels = pixels;
     a.format = format;
-    return v4_scenes_launch(dj, V4BatchKind::kEnvs, a, stream);
+    return v4_batched_launch(dj, V4BatchKind::kEnvs, a, stream);
 }
 
 static_assert(sizeof(pt_v4_frame_range) == sizeof(PtV4FrameRange) && offsetof(pt_v4_frame_range, nframes) == offsetof(PtV4FrameRange, nframes),
@@ -3076,7 +2991,7 @@ static_assert(sizeof(pt_v4_frame_range) == sizeof(PtV4FrameRange) && offsetof(pt
 int pt_v4_render_device_batch(const pt_device_job* dj, const pt_v4_batch* b, void* stream)
 {
     if (!b) return fail(PT_EINVAL, "null batch");
-    return v4_scenes_launch(dj, V4BatchKind::kBatch, *b, stream);
+    return v4_batched_launch(dj, V4BatchKind::kBatch, *b, stream);
 }
 
 int pt_v4_count_device(const pt_device_job* dj, void* stream, pt_work_counts* out)

@@ -243,82 +243,42 @@ constexpr PtKeyList<PtV4Key, kPtV4KeyCount> pt_v4_key_list()
 }
 constexpr PtKeyList<PtV4Key, kPtV4KeyCount> kPtV4Keys = pt_v4_key_list();
 
-// ---- v4 views (pt_v4.hip pt_v4_views_kernel <env, layout, fexp>) ----
-// A batch of views runs the per-tile pool's generic form only: uncounted, a row layout, the sampling
-// flags and the pixel output at run time.  A list of its own: kPtV4Keys stays what one-camera jobs reach.
-struct PtV4ViewsKey {
+// ---- the batched v4 launches (pt_v4.hip pt_v4_views_kernel / _scenes_ / _envs_ / _batch_ <env, layout, fexp>) ----
+// What travels per view: kViews a camera, kScenes also a scene, kEnvs also an env map, kBatch also a frame
+// range.  Each kind runs the per-tile pool's generic form only: uncounted, a row layout, the sampling flags
+// and the pixel output at run time.  An envs launch has no meaning without an env term, so its ENV is
+// equirect or cubemap; the batch launch (the superset) has an instance for every env term, none included.
+// A list of its own: kPtV4Keys stays what one-camera jobs reach.
+enum class PtV4BatchKind { kViews, kScenes, kEnvs, kBatch };
+constexpr int kPtV4BatchKinds = 4;
+struct PtV4BatchedKey {
+    PtV4BatchKind kind;
     int env, layout, fexp;
-    constexpr bool operator==(const PtV4ViewsKey& o) const { return env == o.env && layout == o.layout && fexp == o.fexp; }
+    constexpr bool operator==(const PtV4BatchedKey& o) const
+    {
+        return kind == o.kind && env == o.env && layout == o.layout && fexp == o.fexp;
+    }
 };
-constexpr bool pt_pick_v4_views_valid(int env, int layout) { return env >= 0 && env < 3 && layout >= 0 && layout < kPickTiled; }
-constexpr PtV4ViewsKey pt_pick_v4_views_key(int env, int layout, bool fast_exp) { return {env, layout, fast_exp ? 1 : 0}; }
-constexpr size_t kPtV4ViewsKeyCount = 3 * 2 * 2;
-constexpr PtKeyList<PtV4ViewsKey, kPtV4ViewsKeyCount> pt_v4_views_key_list()
+constexpr bool pt_pick_v4_batched_valid(PtV4BatchKind kind, int env, int layout)
 {
-    PtKeyList<PtV4ViewsKey, kPtV4ViewsKeyCount> l{};
+    return env >= (kind == PtV4BatchKind::kEnvs ? 1 : 0) && env < 3 && layout >= 0 && layout < kPickTiled;
+}
+constexpr PtV4BatchedKey pt_pick_v4_batched_key(PtV4BatchKind kind, int env, int layout, bool fast_exp)
+{
+    return {kind, env, layout, fast_exp ? 1 : 0};
+}
+constexpr size_t kPtV4BatchedKeyCount = 12 + 12 + 8 + 12;
+constexpr PtKeyList<PtV4BatchedKey, kPtV4BatchedKeyCount> pt_v4_batched_key_list()
+{
+    PtKeyList<PtV4BatchedKey, kPtV4BatchedKeyCount> l{};
     size_t n = 0;
-    for (int env = 0; env < 3; ++env)
-        for (int layout = 0; layout < kPickTiled; ++layout)
-            for (int fexp = 1; fexp >= 0; --fexp) l.k[n++] = {env, layout, fexp};
+    for (int kind = 0; kind < kPtV4BatchKinds; ++kind)
+        for (int env = 0; env < 3; ++env)
+            for (int layout = 0; layout < kPickTiled; ++layout)
+                for (int fexp = 1; fexp >= 0; --fexp)
+                    if (pt_pick_v4_batched_valid((PtV4BatchKind)kind, env, layout)) l.k[n++] = {(PtV4BatchKind)kind, env, layout, fexp};
     return l;
 }
-constexpr PtKeyList<PtV4ViewsKey, kPtV4ViewsKeyCount> kPtV4ViewsKeys = pt_v4_views_key_list();
-
-// ---- v4 scenes (pt_v4.hip pt_v4_scenes_kernel <env, layout, fexp>) ----
-// A batch of scenes runs the same generic form as a batch of views, with the scene as a per-view record:
-// the same 12 keys, in a list of its own (its instances are other kernels).
-struct PtV4ScenesKey {
-    int env, layout, fexp;
-    constexpr bool operator==(const PtV4ScenesKey& o) const { return env == o.env && layout == o.layout && fexp == o.fexp; }
-};
-constexpr PtV4ScenesKey pt_pick_v4_scenes_key(int env, int layout, bool fast_exp) { return {env, layout, fast_exp ? 1 : 0}; }
-constexpr size_t kPtV4ScenesKeyCount = kPtV4ViewsKeyCount;
-constexpr PtKeyList<PtV4ScenesKey, kPtV4ScenesKeyCount> pt_v4_scenes_key_list()
-{
-    PtKeyList<PtV4ScenesKey, kPtV4ScenesKeyCount> l{};
-    for (size_t i = 0; i < kPtV4ScenesKeyCount; ++i) l.k[i] = {kPtV4ViewsKeys.k[i].env, kPtV4ViewsKeys.k[i].layout, kPtV4ViewsKeys.k[i].fexp};
-    return l;
-}
-constexpr PtKeyList<PtV4ScenesKey, kPtV4ScenesKeyCount> kPtV4ScenesKeys = pt_v4_scenes_key_list();
-
-// ---- v4 envs (pt_v4.hip pt_v4_envs_kernel <env, layout, fexp>) ----
-// A batch of env maps runs the scenes form with the texture as a per-view record.  It has no meaning
-// without an env term, so ENV is equirect or cubemap: 8 keys, in a list of its own.
-struct PtV4EnvsKey {
-    int env, layout, fexp;
-    constexpr bool operator==(const PtV4EnvsKey& o) const { return env == o.env && layout == o.layout && fexp == o.fexp; }
-};
-constexpr bool pt_pick_v4_envs_valid(int env, int layout) { return env >= 1 && env < 3 && layout >= 0 && layout < kPickTiled; }
-constexpr PtV4EnvsKey pt_pick_v4_envs_key(int env, int layout, bool fast_exp) { return {env, layout, fast_exp ? 1 : 0}; }
-constexpr size_t kPtV4EnvsKeyCount = 2 * 2 * 2;
-constexpr PtKeyList<PtV4EnvsKey, kPtV4EnvsKeyCount> pt_v4_envs_key_list()
-{
-    PtKeyList<PtV4EnvsKey, kPtV4EnvsKeyCount> l{};
-    size_t n = 0;
-    for (int env = 1; env < 3; ++env)
-        for (int layout = 0; layout < kPickTiled; ++layout)
-            for (int fexp = 1; fexp >= 0; --fexp) l.k[n++] = {env, layout, fexp};
-    return l;
-}
-constexpr PtKeyList<PtV4EnvsKey, kPtV4EnvsKeyCount> kPtV4EnvsKeys = pt_v4_envs_key_list();
-
-// ---- v4 batch (pt_v4.hip pt_v4_batch_kernel <env, layout, fexp>) ----
-// The superset launch (a camera, a scene, an env map and a frame range per view) has an instance for every
-// env term, none included: 12 keys, in a list of its own.
-struct PtV4BatchKey {
-    int env, layout, fexp;
-    constexpr bool operator==(const PtV4BatchKey& o) const { return env == o.env && layout == o.layout && fexp == o.fexp; }
-};
-constexpr bool pt_pick_v4_batch_valid(int env, int layout) { return env >= 0 && env < 3 && layout >= 0 && layout < kPickTiled; }
-constexpr PtV4BatchKey pt_pick_v4_batch_key(int env, int layout, bool fast_exp) { return {env, layout, fast_exp ? 1 : 0}; }
-constexpr size_t kPtV4BatchKeyCount = 3 * 2 * 2;
-constexpr PtKeyList<PtV4BatchKey, kPtV4BatchKeyCount> pt_v4_batch_key_list()
-{
-    PtKeyList<PtV4BatchKey, kPtV4BatchKeyCount> l{};
-    size_t n = 0;
-    for (int env = 0; env < 3; ++env)
-        for (int layout = 0; layout < kPickTiled; ++layout)
-            for (int fexp = 1; fexp >= 0; --fexp) l.k[n++] = {env, layout, fexp};
-    return l;
-}
-constexpr PtKeyList<PtV4BatchKey, kPtV4BatchKeyCount> kPtV4BatchKeys = pt_v4_batch_key_list();
+constexpr PtKeyList<PtV4BatchedKey, kPtV4BatchedKeyCount> kPtV4BatchedKeys = pt_v4_batched_key_list();
+static_assert(kPtV4BatchedKeys.k[kPtV4BatchedKeyCount - 1] == PtV4BatchedKey{PtV4BatchKind::kBatch, 2, 1, 0},
+              "44 instances: the last is the batch kind's cubemap, planar8, exact-exp one");

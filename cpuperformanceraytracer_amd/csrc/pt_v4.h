@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pt_kernel_pick.h"
 #include "pt_v4_skywin.h"
 
 #define PT_V4_MAX_OBJECTS 12   // MAX_OBJECTS / MAX_MATERIALS, v4 :351-352
@@ -142,9 +143,6 @@ struct PtV4Views {
                              // job.pix_xrgb), or nullptr: none
     uint32_t grid_cap;       // test knob: at most this many blocks (0: the resident grid)
 };
-// The generic instances (ENV x row layout x FEXP), unscheduled (job.order, units, cost: nullptr), a
-// plain launch.  job.ncols == job.width, job.col0 == 0 (a device job).
-hipError_t pt_launch_v4_views(const PtV4Job& job, const PtV4Scene& scene, const PtV4Views& views, hipStream_t stream);
 
 // ---- a batch of scenes in one launch (pt_v4_render_device_scenes; pt_v4.hip pt_v4_scenes_kernel) ----
 // A views launch whose views each name a scene: the scene is a record of a device table instead of a
@@ -168,10 +166,6 @@ struct PtV4Scenes {
     int32_t nscenes;
     const int32_t* scene_of_view;    // device memory, one entry per view, each in [0, nscenes)
 };
-// The preparation kernel and then the render kernel on `stream`: the generic instances (ENV x row layout x
-// FEXP) of pt_v4_scenes_kernel, launched as pt_launch_v4_views launches its own (unscheduled, a plain
-// launch, views.grid_cap honoured).
-hipError_t pt_launch_v4_scenes(const PtV4Job& job, const PtV4Views& views, const PtV4Scenes& scenes, hipStream_t stream);
 
 // ---- a batch of env maps in one launch (pt_v4_render_device_envs; pt_v4.hip pt_v4_envs_kernel) ----
 // A scenes launch whose views each name a texture of an env set (pt_capi.cpp pt_v4_env_set): the texture
@@ -189,10 +183,6 @@ struct PtV4Envs {
     int32_t nenvs;
     const int32_t* env_of_view;    // device memory, one entry per view, each in [0, nenvs)
 };
-// pt_launch_v4_scenes with the texture per view: the instances (ENV equirect / cubemap x row layout x FEXP)
-// of pt_v4_envs_kernel.  job.env_mode is not NONE; job.env, env_w and env_h are not read.
-hipError_t pt_launch_v4_envs(const PtV4Job& job, const PtV4Views& views, const PtV4Scenes& scenes, const PtV4Envs& envs,
-                             hipStream_t stream);
 
 // ---- a batch with a frame range per view (pt_v4_render_device_batch; pt_v4.hip pt_v4_batch_kernel) ----
 // The superset of the three launches above: a view is (camera, scene, environment, frame range).  View v
@@ -211,7 +201,16 @@ static_assert(sizeof(PtV4FrameRange) == 8, "a frame range record is 8 B");
 struct PtV4Frames {
     const PtV4FrameRange* range_of_view;   // device memory, one record per view
 };
-// pt_launch_v4_envs with the range per view: the instances (ENV x row layout x FEXP, 12) of
-// pt_v4_batch_kernel.  The caller launches only when some view has frames.
-hipError_t pt_launch_v4_batch(const PtV4Job& job, const PtV4Views& views, const PtV4Scenes& scenes, const PtV4Envs& envs,
-                              const PtV4Frames& frames, hipStream_t stream);
+
+// ---- the one launch of the four kinds above (pt_kernel_pick.h PtV4BatchKind, kPtV4BatchedKeys) ----
+// The generic instances (ENV x row layout x FEXP) of the kind's kernel, unscheduled (job.order, units, cost:
+// nullptr) and uncounted, a plain launch on `stream`; job.ncols == job.width, job.col0 == 0 (a device job);
+// views.grid_cap honoured.  What a kind reads must be there, the rest may be nullptr:
+//   kViews   `scene` (a kernel argument); job.env / env_w / env_h with an env term
+//   kScenes  `scenes`; job.env / env_w / env_h with an env term
+//   kEnvs    `scenes`, `envs`; job.env_mode is not NONE; job.env, env_w and env_h are not read
+//   kBatch   `scenes`, `frames`, and with an env term `envs`; job.env, env_w, env_h, frame_first and nframes
+//            are not read (the caller launches only when some view has frames)
+// Every kind but kViews runs the preparation kernel (pt_v4_scenes_prep_kernel) on the stream first.
+hipError_t pt_launch_v4_batched(PtV4BatchKind kind, const PtV4Job& job, const PtV4Scene* scene, const PtV4Views& views,
+                                const PtV4Scenes* scenes, const PtV4Envs* envs, const PtV4Frames* frames, hipStream_t stream);

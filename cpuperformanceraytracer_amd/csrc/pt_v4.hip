@@ -945,7 +945,7 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_OCC void pt_v4_kernel(PtV4Job jo
 // A batch of views in one launch (pt_v4_render_device_views, pt_v4.h PtV4Views): the per-tile pool over
 // the tiles of every view.  The generic form only -- the literal-geometry instances carry the default
 // camera -- with the sampling flags and the pixel output at run time: ENV x row layout x FEXP, 12
-// instances of its own (pt_kernel_pick.h kPtV4ViewsKeys), at the plain instances' 5 waves per SIMD.
+// instances of its own (pt_kernel_pick.h kPtV4BatchedKeys, kViews), at the plain instances' 5 waves per SIMD.
 template <int ENV, int LAYOUT, int FEXP>
 __global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_views_kernel(PtV4Job job, PtV4Scene sc, PtV4Views va)
 {
@@ -961,7 +961,7 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_views_kerne
 
 // A batch of scenes in one launch (pt_v4_render_device_scenes, pt_v4.h PtV4Scenes): the views kernel with
 // the scene as a record of the view (V4SceneRec) instead of a kernel argument -- the same 12 instances
-// (pt_kernel_pick.h kPtV4ScenesKeys).  Everything it adds to the pool's body sits under `if constexpr
+// (pt_kernel_pick.h kPtV4BatchedKeys, kScenes).  Everything it adds to the pool's body sits under `if constexpr
 // (SCENES)`.  No block-wide material table: the four waves of a block may be on four scenes at once.
 template <int ENV, int LAYOUT, int FEXP>
 __global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_scenes_kernel(PtV4Job job, PtV4Views va, PtV4Scenes sa)
@@ -978,7 +978,7 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_scenes_kern
 
 // A batch of env maps in one launch (pt_v4_render_device_envs, pt_v4.h PtV4Envs): the scenes kernel with
 // the texture as a record of the view instead of job.env / env_w / env_h -- ENV equirect or cubemap x row
-// layout x FEXP, 8 instances (pt_kernel_pick.h kPtV4EnvsKeys).  Everything it adds to the pool's body sits
+// layout x FEXP, 8 instances (pt_kernel_pick.h kPtV4BatchedKeys, kEnvs).  Everything it adds to the pool's body sits
 // under `if constexpr (ENVS)`.  Nothing of the texture is block-shared: the four waves of a block may be
 // on four textures at once.
 template <int ENV, int LAYOUT, int FEXP>
@@ -996,7 +996,7 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_envs_kernel
 
 // A batch with a frame range per view (pt_v4_render_device_batch, pt_v4.h PtV4Frames): the scenes kernel's
 // text with ENVS wherever there is an env term and the view's own (frame_first, nframes) -- ENV none /
-// equirect / cubemap x row layout x FEXP, 12 instances (pt_kernel_pick.h kPtV4BatchKeys).  Everything it
+// equirect / cubemap x row layout x FEXP, 12 instances (pt_kernel_pick.h kPtV4BatchedKeys, kBatch).  Everything it
 // adds to the pool's body sits under FRAMES.  Nothing of the range is block-shared: the four waves of a
 // block may be on four ranges at once.
 template <int ENV, int LAYOUT, int FEXP>
@@ -1525,65 +1525,32 @@ hipError_t launch_instance(int i, uint32_t grid, hipStream_t st, const PtV4Job& 
     return hipGetLastError();
 }
 
-// The views instances: entry i is the kernel of kPtV4ViewsKeys[i], as above.
-using V4ViewsKernel = void (*)(PtV4Job, PtV4Scene, PtV4Views);
-struct V4ViewsInstance {
-    PtV4ViewsKey key;
-    V4ViewsKernel kern;
+// The batched instances (views, scenes, envs, batch): entry i is the kernel of kPtV4BatchedKeys[i], as the
+// address hipLaunchKernel takes -- the four kinds' kernels differ in their parameters.  V4Batched makes an
+// entry's key and its address from the same template arguments.
+template <PtV4BatchKind KIND, int ENV, int LAYOUT, int FEXP>
+struct V4Batched {
+    static constexpr PtV4BatchedKey key{KIND, ENV, LAYOUT, FEXP};
+    static const void* kern()
+    {
+        if constexpr (KIND == PtV4BatchKind::kViews) return (const void*)pt_v4_views_kernel<ENV, LAYOUT, FEXP>;
+        else if constexpr (KIND == PtV4BatchKind::kScenes) return (const void*)pt_v4_scenes_kernel<ENV, LAYOUT, FEXP>;
+        else if constexpr (KIND == PtV4BatchKind::kEnvs) return (const void*)pt_v4_envs_kernel<ENV, LAYOUT, FEXP>;
+        else return (const void*)pt_v4_batch_kernel<ENV, LAYOUT, FEXP>;
+    }
 };
+template <size_t I>
+using V4BatchedAt = V4Batched<kPtV4BatchedKeys.k[I].kind, kPtV4BatchedKeys.k[I].env, kPtV4BatchedKeys.k[I].layout, kPtV4BatchedKeys.k[I].fexp>;
+template <typename Seq>
+struct V4BatchedTable;
 template <size_t... I>
-constexpr PtKeyList<V4ViewsInstance, sizeof...(I)> v4_views_table(std::index_sequence<I...>)
-{
-    constexpr auto& k = kPtV4ViewsKeys.k;
-    return {{V4ViewsInstance{k[I], pt_v4_views_kernel<k[I].env, k[I].layout, k[I].fexp>}...}};
-}
-constexpr auto kV4ViewsTable = v4_views_table(std::make_index_sequence<kPtV4ViewsKeyCount>{});
-PtResidentCache<kPtV4ViewsKeyCount> v4_views_resident;
-
-// The scenes instances: entry i is the kernel of kPtV4ScenesKeys[i], as above.
-using V4ScenesKernel = void (*)(PtV4Job, PtV4Views, PtV4Scenes);
-struct V4ScenesInstance {
-    PtV4ScenesKey key;
-    V4ScenesKernel kern;
+struct V4BatchedTable<std::index_sequence<I...>> {
+    static constexpr bool matches = ((V4BatchedAt<I>::key == kPtV4BatchedKeys.k[I]) && ...);
+    const void* kern[sizeof...(I)] = {V4BatchedAt<I>::kern()...};
 };
-template <size_t... I>
-constexpr PtKeyList<V4ScenesInstance, sizeof...(I)> v4_scenes_table(std::index_sequence<I...>)
-{
-    constexpr auto& k = kPtV4ScenesKeys.k;
-    return {{V4ScenesInstance{k[I], pt_v4_scenes_kernel<k[I].env, k[I].layout, k[I].fexp>}...}};
-}
-constexpr auto kV4ScenesTable = v4_scenes_table(std::make_index_sequence<kPtV4ScenesKeyCount>{});
-PtResidentCache<kPtV4ScenesKeyCount> v4_scenes_resident;
-
-// The envs instances: entry i is the kernel of kPtV4EnvsKeys[i], as above.
-using V4EnvsKernel = void (*)(PtV4Job, PtV4Views, PtV4Scenes, PtV4Envs);
-struct V4EnvsInstance {
-    PtV4EnvsKey key;
-    V4EnvsKernel kern;
-};
-template <size_t... I>
-constexpr PtKeyList<V4EnvsInstance, sizeof...(I)> v4_envs_table(std::index_sequence<I...>)
-{
-    constexpr auto& k = kPtV4EnvsKeys.k;
-    return {{V4EnvsInstance{k[I], pt_v4_envs_kernel<k[I].env, k[I].layout, k[I].fexp>}...}};
-}
-constexpr auto kV4EnvsTable = v4_envs_table(std::make_index_sequence<kPtV4EnvsKeyCount>{});
-PtResidentCache<kPtV4EnvsKeyCount> v4_envs_resident;
-
-// The batch instances: entry i is the kernel of kPtV4BatchKeys[i], as above.
-using V4BatchKernel = void (*)(PtV4Job, PtV4Views, PtV4Scenes, PtV4Envs, PtV4Frames);
-struct V4BatchInstance {
-    PtV4BatchKey key;
-    V4BatchKernel kern;
-};
-template <size_t... I>
-constexpr PtKeyList<V4BatchInstance, sizeof...(I)> v4_batch_table(std::index_sequence<I...>)
-{
-    constexpr auto& k = kPtV4BatchKeys.k;
-    return {{V4BatchInstance{k[I], pt_v4_batch_kernel<k[I].env, k[I].layout, k[I].fexp>}...}};
-}
-constexpr auto kV4BatchTable = v4_batch_table(std::make_index_sequence<kPtV4BatchKeyCount>{});
-PtResidentCache<kPtV4BatchKeyCount> v4_batch_resident;
+const V4BatchedTable<std::make_index_sequence<kPtV4BatchedKeyCount>> kV4BatchedTable;
+static_assert(kV4BatchedTable.matches, "the table holds the listed keys, in their order");
+PtResidentCache<kPtV4BatchedKeyCount> v4_batched_resident;
 
 }  // namespace
 
@@ -1635,94 +1602,39 @@ hipError_t pt_launch_v4(const PtV4Job& j_in, const PtV4Scene& sc, hipStream_t st
     return launch_instance(i, pt_pick_grid((uint32_t)r, tiles, kWaves), st, j, sc);
 }
 
-hipError_t pt_launch_v4_views(const PtV4Job& j, const PtV4Scene& sc, const PtV4Views& va, hipStream_t st)
+hipError_t pt_launch_v4_batched(PtV4BatchKind kind, const PtV4Job& j, const PtV4Scene* sc, const PtV4Views& va, const PtV4Scenes* sa,
+                                const PtV4Envs* ea, const PtV4Frames* fa, hipStream_t st)
 {
-    if (j.ncols <= 0 || j.nrows <= 0 || j.nframes <= 0) return hipSuccess;
+    const bool views = kind == PtV4BatchKind::kViews, batch = kind == PtV4BatchKind::kBatch;
+    const bool env_term = j.env_mode != PT_V4_ENV_NONE_;
+    const bool env_table = kind == PtV4BatchKind::kEnvs || (batch && env_term);   // the texture: a record of `ea`, else job.env
+    // (job.nframes is not read by a batch launch: the caller knows that some view has frames)
+    if (j.ncols <= 0 || j.nrows <= 0 || (!batch && j.nframes <= 0)) return hipSuccess;
     if (!va.table || va.nviews < 1 || j.col0 != 0 || j.ncols != j.width) return hipErrorInvalidValue;
-    if (sc.nquads < 0 || sc.nspheres < 0 || sc.nquads + sc.nspheres > PT_V4_MAX_OBJECTS) return hipErrorInvalidValue;
-    if (j.env_mode != PT_V4_ENV_NONE_ && (!j.env || j.env_w <= 0 || j.env_h <= 0)) return hipErrorInvalidValue;
+    if (views ? !sc || sc->nquads < 0 || sc->nspheres < 0 || sc->nquads + sc->nspheres > PT_V4_MAX_OBJECTS
+              : !sa || !sa->table || sa->nscenes < 1 || !sa->scene_of_view)
+        return hipErrorInvalidValue;
+    if (env_table ? !ea || !ea->table || ea->nenvs < 1 || !ea->env_of_view : env_term && (!j.env || j.env_w <= 0 || j.env_h <= 0))
+        return hipErrorInvalidValue;
+    if (batch && (!fa || !fa->range_of_view)) return hipErrorInvalidValue;
     if (!j.queue || j.order || j.units || j.cost || j.counters) return hipErrorInvalidValue;   // unscheduled, uncounted
-    if (!pt_pick_v4_views_valid(j.env_mode, j.layout)) return hipErrorInvalidValue;
+    if (!pt_pick_v4_batched_valid(kind, j.env_mode, j.layout)) return hipErrorInvalidValue;
     const uint64_t tiles = (uint64_t)((j.ncols + 7) / 8) * (uint64_t)((j.nrows + 7) / 8) * (uint64_t)va.nviews;
     if (tiles > PT_TILE_MASK) return hipErrorInvalidValue;   // (a queue entry carries view * tiles + tile)
-    const int i = kPtV4ViewsKeys.find(pt_pick_v4_views_key(j.env_mode, j.layout, j.fast_exp != 0));
-    const int r = i < 0 ? 0 : v4_views_resident.get((size_t)i, (const void*)kV4ViewsTable.k[i].kern, 64 * kWaves);
+    const int i = kPtV4BatchedKeys.find(pt_pick_v4_batched_key(kind, j.env_mode, j.layout, j.fast_exp != 0));
+    const int r = i < 0 ? 0 : v4_batched_resident.get((size_t)i, kV4BatchedTable.kern[i], 64 * kWaves);
     if (r <= 0) return i < 0 ? hipErrorInvalidValue : hipErrorInvalidDevice;
     uint32_t grid = pt_pick_grid((uint32_t)r, (uint32_t)tiles, kWaves);
     if (va.grid_cap && grid > va.grid_cap) grid = va.grid_cap;
-    hipLaunchKernelGGL(kV4ViewsTable.k[i].kern, dim3(grid), dim3(64 * kWaves), 0, st, j, sc, va);
-    return hipGetLastError();
-}
-
-hipError_t pt_launch_v4_scenes(const PtV4Job& j, const PtV4Views& va, const PtV4Scenes& sa, hipStream_t st)
-{
-    if (j.ncols <= 0 || j.nrows <= 0 || j.nframes <= 0) return hipSuccess;
-    if (!va.table || va.nviews < 1 || j.col0 != 0 || j.ncols != j.width) return hipErrorInvalidValue;
-    if (!sa.table || sa.nscenes < 1 || !sa.scene_of_view) return hipErrorInvalidValue;
-    if (j.env_mode != PT_V4_ENV_NONE_ && (!j.env || j.env_w <= 0 || j.env_h <= 0)) return hipErrorInvalidValue;
-    if (!j.queue || j.order || j.units || j.cost || j.counters) return hipErrorInvalidValue;   // unscheduled, uncounted
-    if (!pt_pick_v4_views_valid(j.env_mode, j.layout)) return hipErrorInvalidValue;
-    const uint64_t tiles = (uint64_t)((j.ncols + 7) / 8) * (uint64_t)((j.nrows + 7) / 8) * (uint64_t)va.nviews;
-    if (tiles > PT_TILE_MASK) return hipErrorInvalidValue;   // (a queue entry carries view * tiles + tile)
-    const int i = kPtV4ScenesKeys.find(pt_pick_v4_scenes_key(j.env_mode, j.layout, j.fast_exp != 0));
-    const int r = i < 0 ? 0 : v4_scenes_resident.get((size_t)i, (const void*)kV4ScenesTable.k[i].kern, 64 * kWaves);
-    if (r <= 0) return i < 0 ? hipErrorInvalidValue : hipErrorInvalidDevice;
-    uint32_t grid = pt_pick_grid((uint32_t)r, (uint32_t)tiles, kWaves);
-    if (va.grid_cap && grid > va.grid_cap) grid = va.grid_cap;
-    // the records' material constants first (same stream: the render kernel starts after it)
-    const uint32_t rows = (uint32_t)sa.nscenes * PT_V4_MAX_OBJECTS;
-    hipLaunchKernelGGL(pt_v4_scenes_prep_kernel, dim3((rows + 255u) / 256u), dim3(256), 0, st, sa.table, sa.nscenes);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kV4ScenesTable.k[i].kern, dim3(grid), dim3(64 * kWaves), 0, st, j, va, sa);
-    return hipGetLastError();
-}
-
-hipError_t pt_launch_v4_envs(const PtV4Job& j, const PtV4Views& va, const PtV4Scenes& sa, const PtV4Envs& ea, hipStream_t st)
-{
-    if (j.ncols <= 0 || j.nrows <= 0 || j.nframes <= 0) return hipSuccess;
-    if (!va.table || va.nviews < 1 || j.col0 != 0 || j.ncols != j.width) return hipErrorInvalidValue;
-    if (!sa.table || sa.nscenes < 1 || !sa.scene_of_view) return hipErrorInvalidValue;
-    if (!ea.table || ea.nenvs < 1 || !ea.env_of_view) return hipErrorInvalidValue;
-    if (!j.queue || j.order || j.units || j.cost || j.counters) return hipErrorInvalidValue;   // unscheduled, uncounted
-    if (!pt_pick_v4_envs_valid(j.env_mode, j.layout)) return hipErrorInvalidValue;
-    const uint64_t tiles = (uint64_t)((j.ncols + 7) / 8) * (uint64_t)((j.nrows + 7) / 8) * (uint64_t)va.nviews;
-    if (tiles > PT_TILE_MASK) return hipErrorInvalidValue;   // (a queue entry carries view * tiles + tile)
-    const int i = kPtV4EnvsKeys.find(pt_pick_v4_envs_key(j.env_mode, j.layout, j.fast_exp != 0));
-    const int r = i < 0 ? 0 : v4_envs_resident.get((size_t)i, (const void*)kV4EnvsTable.k[i].kern, 64 * kWaves);
-    if (r <= 0) return i < 0 ? hipErrorInvalidValue : hipErrorInvalidDevice;
-    uint32_t grid = pt_pick_grid((uint32_t)r, (uint32_t)tiles, kWaves);
-    if (va.grid_cap && grid > va.grid_cap) grid = va.grid_cap;
-    // the records' material constants first, as pt_launch_v4_scenes
-    const uint32_t rows = (uint32_t)sa.nscenes * PT_V4_MAX_OBJECTS;
-    hipLaunchKernelGGL(pt_v4_scenes_prep_kernel, dim3((rows + 255u) / 256u), dim3(256), 0, st, sa.table, sa.nscenes);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kV4EnvsTable.k[i].kern, dim3(grid), dim3(64 * kWaves), 0, st, j, va, sa, ea);
-    return hipGetLastError();
-}
-
-hipError_t pt_launch_v4_batch(const PtV4Job& j, const PtV4Views& va, const PtV4Scenes& sa, const PtV4Envs& ea, const PtV4Frames& fa,
-                              hipStream_t st)
-{
-    if (j.ncols <= 0 || j.nrows <= 0) return hipSuccess;   // (job.nframes is not read: the caller knows that some view has frames)
-    if (!va.table || va.nviews < 1 || j.col0 != 0 || j.ncols != j.width) return hipErrorInvalidValue;
-    if (!sa.table || sa.nscenes < 1 || !sa.scene_of_view || !fa.range_of_view) return hipErrorInvalidValue;
-    if (j.env_mode != PT_V4_ENV_NONE_ && (!ea.table || ea.nenvs < 1 || !ea.env_of_view)) return hipErrorInvalidValue;
-    if (!j.queue || j.order || j.units || j.cost || j.counters) return hipErrorInvalidValue;   // unscheduled, uncounted
-    if (!pt_pick_v4_batch_valid(j.env_mode, j.layout)) return hipErrorInvalidValue;
-    const uint64_t tiles = (uint64_t)((j.ncols + 7) / 8) * (uint64_t)((j.nrows + 7) / 8) * (uint64_t)va.nviews;
-    if (tiles > PT_TILE_MASK) return hipErrorInvalidValue;   // (a queue entry carries view * tiles + tile)
-    const int i = kPtV4BatchKeys.find(pt_pick_v4_batch_key(j.env_mode, j.layout, j.fast_exp != 0));
-    const int r = i < 0 ? 0 : v4_batch_resident.get((size_t)i, (const void*)kV4BatchTable.k[i].kern, 64 * kWaves);
-    if (r <= 0) return i < 0 ? hipErrorInvalidValue : hipErrorInvalidDevice;
-    uint32_t grid = pt_pick_grid((uint32_t)r, (uint32_t)tiles, kWaves);
-    if (va.grid_cap && grid > va.grid_cap) grid = va.grid_cap;
-    // the records' material constants first, as pt_launch_v4_scenes
-    const uint32_t rows = (uint32_t)sa.nscenes * PT_V4_MAX_OBJECTS;
-    hipLaunchKernelGGL(pt_v4_scenes_prep_kernel, dim3((rows + 255u) / 256u), dim3(256), 0, st, sa.table, sa.nscenes);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kV4BatchTable.k[i].kern, dim3(grid), dim3(64 * kWaves), 0, st, j, va, sa, ea, fa);
-    return hipGetLastError();
+    if (!views) {
+        // the records' material constants first (same stream: the render kernel starts after it)
+        const uint32_t rows = (uint32_t)sa->nscenes * PT_V4_MAX_OBJECTS;
+        hipLaunchKernelGGL(pt_v4_scenes_prep_kernel, dim3((rows + 255u) / 256u), dim3(256), 0, st, sa->table, sa->nscenes);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    // the kernel's parameters, in its order: (job, scene, views) or (job, views, scenes[, envs[, frames]])
+    const PtV4Envs no_envs{nullptr, 0, nullptr};   // (a batch launch without an env term: not read)
+    const void* const args[5] = {&j, views ? (const void*)sc : &va, views ? (const void*)&va : sa, env_table ? ea : &no_envs, fa};
+    return hipLaunchKernel(kV4BatchedTable.kern[i], dim3(grid), dim3(64 * kWaves), const_cast<void**>(args), 0, st);
 }

@@ -317,7 +317,7 @@
                 va.pix[(size_t)view * (size_t)job.nrows * (size_t)job.width + po] = pt_tone::pack<true, true>(acc.x, acc.y, acc.z, job.pix_xrgb != 0);
         }
     }
-    if constexpr (VIEWS) (void)tile_work;   // (views launches are unscheduled: no cost record, pt_launch_v4_views)
+    if constexpr (VIEWS) (void)tile_work;   // (views launches are unscheduled: no cost record, pt_launch_v4_batched)
     else if (job.cost && lane == 0) pt_record_cost(job.cost, tile, (uint32_t)ntiles, tile_work);
     tile = __builtin_amdgcn_readfirstlane(next_tile);
     }

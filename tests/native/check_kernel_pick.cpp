@@ -238,6 +238,44 @@ int main()
     for (size_t i = 0; i < kPtKeyCount; ++i) CHECK(kPtKeys.find(kPtKeys.k[i]) == (int)i);
     for (size_t i = 0; i < kPtV4KeyCount; ++i) CHECK(kPtV4Keys.find(kPtV4Keys.k[i]) == (int)i);
 
+    // ---- the batched v4 launches: kinds 0 views, 1 scenes, 2 envs, 3 batch; 12 + 12 + 8 + 12 instances
+    CHECK(kPtV4BatchedKeyCount == 44 && kPtV4BatchedKeys.size == 44);
+    CHECK((int)PtV4BatchKind::kViews == 0 && (int)PtV4BatchKind::kScenes == 1 && (int)PtV4BatchKind::kEnvs == 2 &&
+          (int)PtV4BatchKind::kBatch == 3);
+    for (size_t i = 0; i < kPtV4BatchedKeyCount; ++i) CHECK(kPtV4BatchedKeys.find(kPtV4BatchedKeys.k[i]) == (int)i);   // no key twice
+    {
+        int valid = 0, per_kind[4] = {0, 0, 0, 0};
+        for (int kind = 0; kind < 4; ++kind)
+            for (int env = -1; env <= 3; ++env)
+                for (int layout = -1; layout <= 3; ++layout) {
+                    const PtV4BatchKind k = (PtV4BatchKind)kind;
+                    // written out: a row layout (0, 1), env in [0, 3), and an envs launch has an env term
+                    const bool expect = (layout == 0 || layout == 1) && (env == 0 || env == 1 || env == 2) && !(kind == 2 && env == 0);
+                    CHECK(pt_pick_v4_batched_valid(k, env, layout) == expect);
+                    for (int fe = 0; fe < 2; ++fe) {
+                        const PtV4BatchedKey key = pt_pick_v4_batched_key(k, env, layout, fe != 0);
+                        CHECK(key.kind == k && key.env == env && key.layout == layout && key.fexp == fe);   // fast_exp -> fexp 1 / 0
+                        int found = 0;
+                        for (size_t i = 0; i < kPtV4BatchedKeyCount; ++i) found += kPtV4BatchedKeys.k[i] == key;
+                        CHECK(found == (expect ? 1 : 0));   // a valid key at exactly one index, an invalid one nowhere
+                        valid += expect;
+                        per_kind[kind] += expect;
+                    }
+                }
+        CHECK(valid == 44 && per_kind[0] == 12 && per_kind[1] == 12 && per_kind[2] == 8 && per_kind[3] == 12);
+    }
+    CHECK(!pt_pick_v4_batched_valid(PtV4BatchKind::kEnvs, 0, 0) && !pt_pick_v4_batched_valid(PtV4BatchKind::kEnvs, 0, 1));   // envs, env none
+    CHECK(pt_pick_v4_batched_valid(PtV4BatchKind::kEnvs, 1, 0) && pt_pick_v4_batched_valid(PtV4BatchKind::kBatch, 0, 1));
+    for (int kind = 0; kind < 4; ++kind) {
+        CHECK(!pt_pick_v4_batched_valid((PtV4BatchKind)kind, 1, 2));   // the tiled layout
+        CHECK(!pt_pick_v4_batched_valid((PtV4BatchKind)kind, 3, 0) && !pt_pick_v4_batched_valid((PtV4BatchKind)kind, -1, 0));
+    }
+    CHECK(pt_pick_v4_batched_key(PtV4BatchKind::kScenes, 2, 1, true).fexp == 1 && pt_pick_v4_batched_key(PtV4BatchKind::kScenes, 2, 1, false).fexp == 0);
+    // ordered by kind, then env, layout, fast exp first -- as the four lists before them
+    CHECK((kPtV4BatchedKeys.k[0] == PtV4BatchedKey{PtV4BatchKind::kViews, 0, 0, 1}) && (kPtV4BatchedKeys.k[1] == PtV4BatchedKey{PtV4BatchKind::kViews, 0, 0, 0}));
+    CHECK((kPtV4BatchedKeys.k[12] == PtV4BatchedKey{PtV4BatchKind::kScenes, 0, 0, 1}) && (kPtV4BatchedKeys.k[24] == PtV4BatchedKey{PtV4BatchKind::kEnvs, 1, 0, 1}));
+    CHECK((kPtV4BatchedKeys.k[32] == PtV4BatchedKey{PtV4BatchKind::kBatch, 0, 0, 1}) && (kPtV4BatchedKeys.k[43] == PtV4BatchedKey{PtV4BatchKind::kBatch, 2, 1, 0}));
+
     // ---- completeness: every key a valid job can be given exists; the listed keys no job reaches are printed
     static bool hit[kPtKeyCount], hit4[kPtV4KeyCount];
     int jobs = 0, unreached = 0;

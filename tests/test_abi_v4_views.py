@@ -118,6 +118,24 @@ def test_invalid_job(N):
     assert N.load().pt_v4_render_device_views(None, _cams(N, [CAM]), 1, None, 0, None) == N.PT_EINVAL
 
 
+def test_the_first_failing_check_is_reported(N):
+    """Calls that break two rules at once name the earlier one: job, camera array, view count, pixel format, tile
+    entries, each camera, and only then "nothing to render" (which use_env does not disturb).  Codes and texts as
+    the call reported them when it still had a body of its own (recorded from that revision's library)."""
+    pix = ctypes.c_void_p(0x2000)
+    huge = dict(width=16384, height=8192, nrows=8192)
+    bad = ((0.0, 0.0, 40.0), 180.0)
+    assert _call(N, _job(N, buf=None), None, nviews=0) == (N.PT_EINVAL, "null device job/buffer")
+    assert _call(N, _job(N), None, nviews=0) == (N.PT_EINVAL, "null camera array")
+    assert _call(N, _job(N), [CAM], nviews=0, pixels=pix, fmt=7) == (N.PT_EINVAL, "nviews 0 outside [1, 1024]")
+    assert _call(N, _job(N, **huge), [CAM] * 1024, pixels=pix, fmt=7) == (N.PT_EINVAL, "unknown pixel format 7")
+    assert _call(N, _job(N, **huge), [bad] * 1024) == (N.PT_EINVAL, "1024 views x 2097152 tiles exceed the tile queue's 1073741823 entries")
+    assert _call(N, _job(N, nframes=0), [CAM, bad]) == (N.PT_EINVAL, "view 1: fov_degrees 180 outside (0, 180)")
+    assert _call(N, _job(N, frame_first=0), [CAM]) == (N.PT_EINVAL, "frame range [0, +8) invalid")
+    assert _call(N, _job(N, nframes=0, use_env=1), [CAM])[0] == N.PT_OK
+    assert _call(N, _job(N, nrows=0, use_env=1), [CAM])[0] == N.PT_OK
+
+
 def test_a_rejected_view_is_named_and_the_global_camera_is_untouched(N):
     before = _get_camera(N)
     cams = [CAM, ((3.0, -2.0, 30.0), 60.0), ((0.0, 0.0, 40.0), 180.0), CAM]

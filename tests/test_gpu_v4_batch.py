@@ -313,7 +313,63 @@ def test_row_shard_with_ranges(lib):
     _check(buf, views, 24, 16, frames, nrows=8, rows=tuple(rows.items()))
 
 
-# ---- 8. what is rejected (with a live set: the checks a CPU cannot reach) ---------------------------------------------
+# ---- 8. the four calls share one staging ring ---------------------------------------------------------------------
+VIEW_RING = 4   # pt_capi.cpp kViewRing: the slots of the ring the views, scenes, envs and batch calls stage through
+
+
+def test_interleaved_kinds_share_the_staging_ring(lib):
+    """kViewRing + 2 batched calls back to back on one stream, no synchronisation between them, cycling through the
+    views, scenes and batch calls (no env term is configured, so no envs call): the fifth and sixth reuse the
+    slots of the first and second, which another KIND filled -- a block of another layout.  Each call has its own
+    accumulator and its own pair of cameras, so a slot rewritten while its launch still read it, or a table read
+    at another kind's offsets, shows as another image.  After one synchronisation each accumulator equals, bit for
+    bit, the same call issued alone on a fresh accumulator (GPU against GPU; the oracle has the other tests)."""
+    import torch
+    from cpuperformanceraytracer_amd.device import render_v4_device_batch, render_v4_device_scenes, render_v4_device_views
+    lib(mode="none")
+    w, h, nv = 24, 16, 2
+    kw = dict(frame_first=1, nframes=2, num_bounces=B)
+    two = [_scene("S1"), _scene("S2")]
+    kinds = [lambda buf, cams: render_v4_device_views(buf, cams, w, h, **kw),
+             lambda buf, cams: render_v4_device_scenes(buf, two, cams, w, h, **kw),
+             lambda buf, cams: render_v4_device_batch(buf, cams, w, h, frames=[(1, 2), (1, 2)], scenes=two, scene_of_view=[0, 1],
+                                                      num_bounces=B)]
+    pairs = [("A", "B"), ("C", "D"), ("default", "A"), ("B", "C"), ("D", "default"), ("A", "C")]
+    assert len(pairs) == VIEW_RING + 2 and all(pairs[i] != pairs[i - VIEW_RING] for i in range(VIEW_RING, len(pairs)))
+    calls = [(kinds[i % len(kinds)], [_camera(c) for c in pair]) for i, pair in enumerate(pairs)]
+    together = [torch.zeros((nv, h, w, 3), dtype=torch.float32, device="cuda:0") for _ in calls]
+    alone = [torch.zeros_like(t) for t in together]
+    torch.cuda.synchronize()
+    for (call, cams), buf in zip(calls, together):
+        call(buf, cams)
+    torch.cuda.synchronize()
+    for (call, cams), buf in zip(calls, alone):
+        call(buf, cams)
+        torch.cuda.synchronize()
+    from cpuperformanceraytracer_amd.device import check_device_errors
+    check_device_errors()
+    for i, (t, a) in enumerate(zip(together, alone)):
+        assert bool((a != 0).any()), f"call {i} rendered nothing"
+        assert torch.equal(t.view(torch.int32), a.view(torch.int32)), f"call {i} ({pairs[i]}): back to back != alone"
+    assert not torch.equal(together[0].view(torch.int32), together[3].view(torch.int32)), "two views calls, other cameras"
+
+
+def test_views_call_with_use_env_and_no_env_term_is_a_state_error(lib):
+    """The views call keeps its own rule on the shared host path: use_env under env mode NONE is PT_ESTATE (the
+    batch call renders the ambient there, the envs call says PT_EINVAL).  Code and text as the views call reported
+    them when it still had a body of its own (recorded from that revision's library); nothing is written."""
+    import torch
+    from cpuperformanceraytracer_amd.device import render_v4_device_views
+    lib(mode="none")
+    buf = torch.full((1, 8, 8, 3), 7.0, dtype=torch.float32, device="cuda:0")
+    with pytest.raises(N.PtError) as e:
+        render_v4_device_views(buf, [_camera("A")], 8, 8, frame_first=1, nframes=2, num_bounces=B, use_env=True)
+    assert e.value.code == N.PT_ESTATE and "use_env with v4 env mode NONE" in str(e.value), str(e.value)
+    torch.cuda.synchronize()
+    assert bool((buf == 7.0).all()), "a rejected call wrote the buffer"
+
+
+# ---- 9. what is rejected (with a live set: the checks a CPU cannot reach) ---------------------------------------------
 def test_rejected_with_a_live_set(lib):
     import torch
     make = lib()

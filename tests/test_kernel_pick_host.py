@@ -3,7 +3,10 @@ tests/native/check_kernel_pick.cpp against expectations written out there: the d
 count (single chunk, multi, ring from 48 frames, never for the env kernel), what the tiled layout and
 counted launches exclude, when continuous tiles takes a launch and when the tonemap pass follows; for
 v4 the default camera by bits, DEF / DFL / FEXP, every conjunct of the present rule for device jobs and
-for the drop-in's calls, and the continuous-tiles threshold at a resident grid of 1536 blocks; the grid;
+for the drop-in's calls, and the continuous-tiles threshold at a resident grid of 1536 blocks; for the
+batched v4 launches (views, scenes, envs, batch) that every valid (kind, env, layout, fexp) sits at exactly
+one of the 44 places of their key list and what is invalid (envs without an env term, the tiled layout, an
+unknown env) at none; the grid;
 and, over every combination of the facts, that each picked key is in the key lists the instance tables
 of pt_kernel.hip and pt_v4.hip are built from (the listed keys that no job reaches are printed).
 
