@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = (
     "pt_copy_output_to_file", "pt_v4_render_device", "pt_v4_render_device_chain", "pt_v4_render_device_present",
     "pt_v4_render_device_views", "pt_v4_render_device_scenes", "pt_v4_get_scene_desc", "pt_v4_count_device", "pt_v4_begin_frame",
     "pt_v4_make_env_set", "pt_v4_free_env_set", "pt_v4_render_device_envs", "pt_v4_render_device_batch",
+    "pt_v4_render_device_batch_stats",
     "pt_v4_default_camera", "pt_v4_set_camera", "pt_v4_get_camera", "pt_v4_get_sky_window",
     "pt_make_work_queue", "pt_add_work_queue_entry", "pt_complete_all_work", "pt_complete_all_work_async",
     "pt_wait_work", "pt_work_queue_size", "pt_free_work_queue",
@@ -138,6 +139,11 @@ class PtV4Batch(ctypes.Structure):
                 ("scenes", ctypes.POINTER(PtV4SceneDesc)), ("nscenes", ctypes.c_int32), ("scene_of_view", ctypes.POINTER(ctypes.c_int32)),
                 ("envs", ctypes.c_void_p), ("env_of_view", ctypes.POINTER(ctypes.c_int32)), ("pixels", ctypes.c_void_p),
                 ("format", ctypes.c_int32)]
+
+
+class PtV4ViewStats(ctypes.Structure):
+    """pt_v4_view_stats: how much a view's displayed (8-bit) image moved in one pt_v4_render_device_batch_stats."""
+    _fields_ = [("sum_delta", ctypes.c_uint64), ("changed", ctypes.c_uint32), ("max_delta", ctypes.c_uint32)]
 
 
 class PtError(RuntimeError):
@@ -234,6 +240,7 @@ def load() -> ctypes.CDLL:
         "pt_v4_render_device_envs": (i32, [ctypes.POINTER(PtDeviceJob), vp, ctypes.POINTER(i32), ctypes.POINTER(PtV4SceneDesc), i32,
                                            ctypes.POINTER(i32), ctypes.POINTER(PtV4Camera), i32, vp, i32, vp]),
         "pt_v4_render_device_batch": (i32, [ctypes.POINTER(PtDeviceJob), ctypes.POINTER(PtV4Batch), vp]),
+        "pt_v4_render_device_batch_stats": (i32, [ctypes.POINTER(PtDeviceJob), ctypes.POINTER(PtV4Batch), vp, vp]),
         "pt_v4_count_device": (i32, [ctypes.POINTER(PtDeviceJob), vp, ctypes.POINTER(PtWorkCounts)]),
         "pt_v4_begin_frame": (i32, []),
         "pt_v4_default_camera": (None, [ctypes.POINTER(PtV4Camera)]),

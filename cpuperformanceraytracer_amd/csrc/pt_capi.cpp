@@ -152,6 +152,11 @@ struct Dev {
         size_t cap = 0;                 // bytes of each
         hipEvent_t done = nullptr;
         bool pending = false;           // done has been recorded
+        // pt_v4_render_device_batch_stats under a tonemap pair the render kernel does not fuse: the old slices'
+        // packed pixels (nviews x nrows x width u32), written before the render and read by the compare pass
+        // after it; grown like the block, and `done` is recorded after that pass
+        uint32_t* before = nullptr;
+        size_t before_cap = 0;          // u32 elements
     } batch[kViewRing];
     unsigned batch_next = 0;
     // chained launches (pt_render_device_chain, launch_chain): consecutive launches of one geometry
@@ -411,6 +416,7 @@ const char* guard_name(uint32_t id)
         case PT_G_SCENE: return "scenes launch: scene index beyond the scene table, or a record's object counts beyond MAX_OBJECTS";
         case PT_G_ENV: return "envs launch: env index beyond the env set, or a record's width or height not positive";
         case PT_G_FRAMES: return "batch launch: a view's frame range record is invalid; value: the view";
+        case PT_G_STATS: return "batch launch with statistics: a view's record beyond the statistics buffer; value: the view";
         case PT_G_CAM_INDEX: return "camera-hit cache record outside the geometry's tiles";
         case PT_G_CAM_RECORD: return "a traced camera hit differs from its cached record; value: tile * 64 + lane";
         case PT_G_CHAIN_WAIT: return "chained launch: the previous launch's tile never became ready; value: the tile | its epoch's lag "
@@ -1651,6 +1657,7 @@ void free_dev(Dev& dv)
         if (s.done) (void)hipEventDestroy(s.done);
         if (s.dev) (void)hipFree(s.dev);
         if (s.host) (void)hipHostFree(s.host);
+        if (s.before) (void)hipFree(s.before);
     }
     for (Sched& sc : dv.sched)
         if (sc.used) free_sched(sc);
@@ -2727,9 +2734,31 @@ int pt_v4_get_scene_desc(pt_v4_scene_desc* out)
 //           view when `envs` is given; without a set but with an env term, the process-wide map travels as
 //           a one-record table in the block (with a mapping of zeros), so that the kernel reads a table
 //           either way.
+//   `stats` (pt_v4_render_device_batch_stats; kBatch only): the same call, which also leaves each view's
+//           statistics in `stats` -- cleared on the stream first, also when nothing renders.  Under the default
+//           tonemap pair the batch kind's statistics instances compare as they store (pt_v4.h PtV4Stats); under
+//           any other pair the old slices are packed into the slot's scratch before the render and the compare
+//           pass (pt_output.h PtStatsJob) takes the place of the conversion pass.
 using V4BatchKind = PtV4BatchKind;   // (pt_kernel_pick.h: kViews, kScenes, kEnvs, kBatch)
 
-static int v4_batched_launch(const pt_device_job* dj, V4BatchKind kind, const pt_v4_batch& args, void* stream)
+static_assert(sizeof(pt_v4_view_stats) == sizeof(PtV4ViewStats) && offsetof(pt_v4_view_stats, sum_delta) == offsetof(PtV4ViewStats, sum_delta) &&
+                  offsetof(pt_v4_view_stats, changed) == offsetof(PtV4ViewStats, changed) &&
+                  offsetof(pt_v4_view_stats, max_delta) == offsetof(PtV4ViewStats, max_delta),
+              "pt_v4_view_stats is PtV4ViewStats");
+
+// Nothing renders (every view has 0 frames, or no rows): the records are still cleared on the stream.
+static int v4_stats_clear_only(const pt_device_job* dj, pt_v4_view_stats* stats, int32_t nviews, void* stream)
+{
+    int rc;
+    Dev* dv = nullptr;
+    DeviceGuard guard;
+    if ((rc = ensure_init()) || (rc = dev_of(dj->buf, &dv)) || (rc = use_dev(*dv))) return rc;
+    HIP_TRY(hipMemsetAsync(stats, 0, (size_t)nviews * sizeof(pt_v4_view_stats), (hipStream_t)stream));
+    return PT_OK;
+}
+
+static int v4_batched_launch(const pt_device_job* dj, V4BatchKind kind, const pt_v4_batch& args, void* stream,
+                             pt_v4_view_stats* stats = nullptr)
 {
     const bool views = kind == V4BatchKind::kViews, batch = kind == V4BatchKind::kBatch;
     const bool with_envs = kind == V4BatchKind::kEnvs || (batch && args.envs);   // a texture per view, from an env set
@@ -2813,7 +2842,7 @@ static int v4_batched_launch(const pt_device_job* dj, V4BatchKind kind, const pt
                 return fail(PT_EINVAL, "view %d: frame range [%u, +%d) invalid", v, r.frame_first, r.nframes);
             any = any || r.nframes > 0;
         }
-        if (!any || dj->nrows == 0) return PT_OK;   // nothing to render
+        if (!any || dj->nrows == 0) return stats ? v4_stats_clear_only(dj, stats, nviews, stream) : PT_OK;   // nothing to render
     } else if (dj->nframes == 0 || dj->nrows == 0) {
         return PT_OK;   // nothing to render
     }
@@ -2860,6 +2889,9 @@ static int v4_batched_launch(const pt_device_job* dj, V4BatchKind kind, const pt
     // the render kernel writes the pixels with the default tonemap pair; any other pair: a second pass
     const bool fused = pixels && g.v4cfg.fast_aces && g.v4cfg.fast_gamma;
     j.pix_xrgb = format == PT_PIXEL_XRGB8;
+    // and so with the statistics: compared in the render kernel, or (any other pair) around it
+    const bool stats_fused = stats && g.v4cfg.fast_aces && g.v4cfg.fast_gamma, stats_pass = stats && !stats_fused;
+    if (stats) HIP_TRY(hipMemsetAsync(stats, 0, (size_t)nviews * sizeof(pt_v4_view_stats), st));
 
     const auto up16 = [](size_t n) { return (n + 15u) & ~(size_t)15u; };
     const size_t off_views = up16((size_t)nscenes * sizeof(PtV4SceneRec));
@@ -2891,6 +2923,17 @@ static int v4_batched_launch(const pt_device_job* dj, V4BatchKind kind, const pt
             return fail(PT_ENOMEM, "hipMalloc(batch block, %zu bytes) failed", cap);
         }
         ss.cap = cap;
+    }
+    const size_t npix = (size_t)nviews * (size_t)dj->nrows * (size_t)dj->width;
+    if (stats_pass && ss.before_cap < npix) {   // (likewise: no launch reads the slot's scratch now)
+        if (ss.before) (void)hipFree(ss.before);
+        ss.before = nullptr;
+        ss.before_cap = 0;
+        if (hipMalloc((void**)&ss.before, npix * sizeof(uint32_t)) != hipSuccess) {
+            ss.before = nullptr;
+            return fail(PT_ENOMEM, "hipMalloc(batch statistics scratch, %zu bytes) failed", npix * sizeof(uint32_t));
+        }
+        ss.before_cap = npix;
     }
     PtV4SceneRec* const hrec = reinterpret_cast<PtV4SceneRec*>(ss.host);
     PtV4View* const hview = reinterpret_cast<PtV4View*>(ss.host + off_views);
@@ -2926,15 +2969,35 @@ static int v4_batched_launch(const pt_device_job* dj, V4BatchKind kind, const pt
                         : staged_env ? PtV4Envs{reinterpret_cast<const PtV4EnvRec*>(ss.dev + off_erec), 1, emap}
                                      : PtV4Envs{nullptr, 0, nullptr};
     const PtV4Frames fa{reinterpret_cast<const PtV4FrameRange*>(ss.dev + off_frames)};
+    hipError_t e;
+    if (stats_pass) {
+        // the old slices as the display would show them, before the render overwrites them (after chain_join: a
+        // live chain's last launch may still write them).  The slices lie back to back: one image.
+        e = pt_launch_tonemap(tone_job(j.buf, j.ncols, j.nrows * nviews, j.layout, 0, 0, ss.before, PT_PIXEL_XRGB8), st);
+        if (e != hipSuccess) return fail(PT_EHIP, "tonemap launch failed: %s", hipGetErrorString(e));
+    }
+    const PtV4Stats sta{reinterpret_cast<PtV4ViewStats*>(stats)};
     // (what the kind does not read is not passed; a views launch renders the process-wide scene)
-    hipError_t e = pt_launch_v4_batched(kind, j, views ? &g.v4scene : nullptr, va, views ? nullptr : &sa, ea.table ? &ea : nullptr,
-                                        batch ? &fa : nullptr, st);
+    e = pt_launch_v4_batched(kind, j, views ? &g.v4scene : nullptr, va, views ? nullptr : &sa, ea.table ? &ea : nullptr,
+                             batch ? &fa : nullptr, st, stats_fused ? &sta : nullptr);
     if (e != hipSuccess)
         return fail(PT_EHIP, "v4 %s launch failed: %s", views ? "views" : batch ? "batch" : with_envs ? "envs" : "scenes", hipGetErrorString(e));
     HIP_TRY(hipEventRecord(ss.done, st));
     ss.pending = true;
     if ((rc = queue_done(dv, ls.slot, st, true))) return rc;
-    if (pixels && !fused) {
+    if (stats_pass) {
+        // the new slices against the scratch, per view; it writes the pixels too, so no conversion pass follows
+        PtStatsJob sj{};
+        sj.tone = tone_job(j.buf, j.ncols, j.nrows, j.layout, 0, 0, pixels, format);
+        sj.nviews = nviews;
+        sj.before = ss.before;
+        sj.ranges = fa.range_of_view;
+        sj.stats = sta.of_view;
+        sj.err = j.err;
+        e = pt_launch_tonemap_stats(sj, st);
+        if (e != hipSuccess) return fail(PT_EHIP, "statistics pass launch failed: %s", hipGetErrorString(e));
+        HIP_TRY(hipEventRecord(ss.done, st));   // (again: the pass reads the slot's ranges and scratch)
+    } else if (pixels && !fused) {
         // (the slices lie back to back: one image of nviews x nrows rows in either row layout)
         const PtToneJob tj = tone_job(j.buf, j.ncols, j.nrows * nviews, j.layout, 0, 0, pixels, format);
         e = pt_launch_tonemap(tj, st);
@@ -2992,6 +3055,13 @@ int pt_v4_render_device_batch(const pt_device_job* dj, const pt_v4_batch* b, voi
 {
     if (!b) return fail(PT_EINVAL, "null batch");
     return v4_batched_launch(dj, V4BatchKind::kBatch, *b, stream);
+}
+
+int pt_v4_render_device_batch_stats(const pt_device_job* dj, const pt_v4_batch* b, pt_v4_view_stats* stats, void* stream)
+{
+    if (!b) return fail(PT_EINVAL, "null batch");
+    if (!stats) return fail(PT_EINVAL, "null statistics buffer");
+    return v4_batched_launch(dj, V4BatchKind::kBatch, *b, stream, stats);
 }
 
 int pt_v4_count_device(const pt_device_job* dj, void* stream, pt_work_counts* out)

@@ -115,6 +115,7 @@ enum PtGuardId : uint32_t {
                             // record whose width or height is not positive
     PT_G_FRAMES = 19,       // a batch launch: a view's frame range record with nframes < 0, frame_first < 1 or
                             // frame_first + nframes beyond 2^24; value: the view
+    PT_G_STATS = 20,        // a batch launch with statistics: a view's record beyond the nviews records; value: the view
 };
 
 // Tile queues: one counter per XCD group, 128 B apart (PT_QUEUE_WORDS u32 per launch).

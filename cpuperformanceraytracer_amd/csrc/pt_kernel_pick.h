@@ -282,3 +282,22 @@ constexpr PtKeyList<PtV4BatchedKey, kPtV4BatchedKeyCount> pt_v4_batched_key_list
 constexpr PtKeyList<PtV4BatchedKey, kPtV4BatchedKeyCount> kPtV4BatchedKeys = pt_v4_batched_key_list();
 static_assert(kPtV4BatchedKeys.k[kPtV4BatchedKeyCount - 1] == PtV4BatchedKey{PtV4BatchKind::kBatch, 2, 1, 0},
               "44 instances: the last is the batch kind's cubemap, planar8, exact-exp one");
+
+// ---- the batch launch with per-view statistics (pt_v4.hip pt_v4_batch_stats_kernel <env, layout, fexp>) ----
+// The batch kind's twelve instances once more, each also reducing its tiles' 8-bit differences into the view's
+// record (pt_v4.h PtV4Stats).  A list of its own: kPtV4BatchedKeys and PtV4BatchKind stay what the four plain
+// calls reach, and their instances the code they were.
+constexpr size_t kPtV4BatchStatsKeyCount = 12;
+constexpr PtKeyList<PtV4BatchedKey, kPtV4BatchStatsKeyCount> pt_v4_batch_stats_key_list()
+{
+    PtKeyList<PtV4BatchedKey, kPtV4BatchStatsKeyCount> l{};
+    size_t n = 0;
+    for (int env = 0; env < 3; ++env)
+        for (int layout = 0; layout < kPickTiled; ++layout)
+            for (int fexp = 1; fexp >= 0; --fexp) l.k[n++] = {PtV4BatchKind::kBatch, env, layout, fexp};
+    return l;
+}
+constexpr PtKeyList<PtV4BatchedKey, kPtV4BatchStatsKeyCount> kPtV4BatchStatsKeys = pt_v4_batch_stats_key_list();
+static_assert(kPtV4BatchStatsKeys.k[0] == PtV4BatchedKey{PtV4BatchKind::kBatch, 0, 0, 1} &&
+                  kPtV4BatchStatsKeys.k[kPtV4BatchStatsKeyCount - 1] == PtV4BatchedKey{PtV4BatchKind::kBatch, 2, 1, 0},
+              "12 instances, in the batch kind's order");

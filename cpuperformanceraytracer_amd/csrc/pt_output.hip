@@ -7,7 +7,10 @@
 // (pt_render_device_present: a pixel's value written at its last fold, no second pass).
 // One thread per pixel, any accumulator layout; 12 B read + 4 B written per pixel: HBM-bound.
 #include "pt_output.h"
+#include "pt_guard.h"
 #include "pt_tonemap.h"
+#include "pt_v4.h"
+#include "pt_v4_stats.h"
 #include <algorithm>
 
 namespace {
@@ -60,6 +63,77 @@ hipError_t pt_launch_tonemap(const PtToneJob& j, hipStream_t st)
         case PT_LAYOUT_TILED_PLANAR8:
             if (j.tile_w <= 0 || j.tile_h <= 0) return hipErrorInvalidValue;
             return launch_layout<PT_LAYOUT_TILED_PLANAR8>(j, blocks, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// ---- per-view statistics of a v4 batch: the compare pass (pt_output.h PtStatsJob) -------------------
+namespace {
+
+// blockIdx.y is the view, so a wave never spans two views: each thread sums over its pixels of the view's slice,
+// the wave reduces (integers: any order gives the same result), lane 0 issues the three atomics (pt_v4_stats.h).
+template <int LAYOUT, bool FAST_ACES, bool FAST_GAMMA>
+__global__ __launch_bounds__(256) void pt_tonemap_stats_kernel(PtStatsJob j)
+{
+    const uint32_t view = blockIdx.y;
+    const uint32_t w = (uint32_t)j.tone.width, npix = w * (uint32_t)j.tone.height;
+    const bool counted = j.ranges[view].nframes > 0;
+    if (!counted && !j.tone.out) return;
+    const size_t p0 = (size_t)view * npix;
+    const float* const acc = j.tone.accum + p0 * 3u;
+    unsigned long long sum = 0;
+    uint32_t changed = 0, mx = 0;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += gridDim.x * blockDim.x) {
+        size_t base = (size_t)p * 3u, cs = 1;
+        if (LAYOUT == PT_LAYOUT_PLANAR8) {
+            const uint32_t y = p / w, x = p - y * w;
+            base = ((size_t)y * w + (x & ~7u)) * 3u + (x & 7u);
+            cs = 8;
+        }
+        const float r = acc[base], g = acc[base + cs], b = acc[base + 2 * cs];
+        if (j.tone.out) j.tone.out[p0 + p] = pt_tone::pack<FAST_ACES, FAST_GAMMA>(r, g, b, j.tone.format == PT_PIXEL_XRGB8);
+        if (counted) {
+            const uint32_t d = v4_stats_delta(j.before[p0 + p], pt_tone::pack<FAST_ACES, FAST_GAMMA>(r, g, b, true));
+            sum += d & 0xffffu;
+            changed += d != 0u;
+            mx = max(mx, d >> 16);
+        }
+    }
+    if (!counted) return;   // (block-uniform)
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_xor(sum, off);
+        changed += __shfl_xor(changed, off);
+        mx = max(mx, __shfl_xor(mx, off));
+    }
+    if ((threadIdx.x & 63) == 0 && PT_GUARD(j.err, view < (uint32_t)j.nviews, PT_G_STATS, view))
+        v4_stats_commit(j.stats + view, sum, changed, mx);
+}
+
+template <int LAYOUT>
+hipError_t launch_stats_layout(const PtStatsJob& j, dim3 grid, hipStream_t st)
+{
+    // (the default pair is the render kernel's own: pt_v4.hip pt_v4_batch_stats_kernel)
+    if (j.tone.fast_aces && j.tone.fast_gamma) return hipErrorInvalidValue;
+    if (j.tone.fast_aces) hipLaunchKernelGGL((pt_tonemap_stats_kernel<LAYOUT, true, false>), grid, dim3(256), 0, st, j);
+    else if (j.tone.fast_gamma) hipLaunchKernelGGL((pt_tonemap_stats_kernel<LAYOUT, false, true>), grid, dim3(256), 0, st, j);
+    else hipLaunchKernelGGL((pt_tonemap_stats_kernel<LAYOUT, false, false>), grid, dim3(256), 0, st, j);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t pt_launch_tonemap_stats(const PtStatsJob& j, hipStream_t st)
+{
+    if (j.tone.width <= 0 || j.tone.height <= 0 || j.nviews <= 0) return hipSuccess;
+    if (!j.tone.accum || !j.before || !j.ranges || !j.stats || j.nviews > 65535) return hipErrorInvalidValue;
+    const uint64_t npix = (uint64_t)j.tone.width * (uint64_t)j.tone.height;
+    if (npix > 0xffffffffull) return hipErrorInvalidValue;   // (the kernel's pixel index; `changed` is 32 bits)
+    // a view's blocks: enough for its pixels, together about the conversion pass's grid
+    const uint64_t per_view = std::max<uint64_t>(1, (256u * 16u) / (uint64_t)j.nviews);
+    const dim3 grid((unsigned)std::min<uint64_t>((npix + 255) / 256, per_view), (unsigned)j.nviews);
+    switch (j.tone.layout) {
+        case PT_LAYOUT_INTERLEAVED: return launch_stats_layout<PT_LAYOUT_INTERLEAVED>(j, grid, st);
+        case PT_LAYOUT_PLANAR8: return launch_stats_layout<PT_LAYOUT_PLANAR8>(j, grid, st);
         default: return hipErrorInvalidValue;
     }
 }

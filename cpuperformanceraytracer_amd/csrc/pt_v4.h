@@ -202,6 +202,23 @@ struct PtV4Frames {
     const PtV4FrameRange* range_of_view;   // device memory, one record per view
 };
 
+// ---- per-view statistics of a batch (pt_v4_render_device_batch_stats; pt_v4.hip pt_v4_batch_stats_kernel) ----
+// How much each view's DISPLAYED image moved in the launch: `before` is the 8-bit value (pt_tonemap.h, the default
+// fast ACES / gamma) of a pixel's accumulator as the launch finds it, `after` of the value it stores; R, G, B only.
+// At a tile's end each lane with a pixel packs both, the wave reduces (pt_v4_stats.h) and one lane issues three
+// integer atomics on the view's record -- one tile is one wave and one view.  The old value is re-read from the
+// slice just before the store (the slice is untouched until then: one writer per pixel), so nothing more is live
+// through the pool loop.  A view of 0 frames issues nothing: the host cleared the records on the stream.
+struct PtV4ViewStats {
+    unsigned long long sum_delta;   // sum over pixels and R, G, B of |after - before|
+    uint32_t changed;               // pixels whose R, G, B differ
+    uint32_t max_delta;             // largest |after - before| of one channel
+};
+static_assert(sizeof(PtV4ViewStats) == 16, "a statistics record is 16 B");
+struct PtV4Stats {
+    PtV4ViewStats* of_view;   // device memory, one record per view, zero at the launch's start
+};
+
 // ---- the one launch of the four kinds above (pt_kernel_pick.h PtV4BatchKind, kPtV4BatchedKeys) ----
 // The generic instances (ENV x row layout x FEXP) of the kind's kernel, unscheduled (job.order, units, cost:
 // nullptr) and uncounted, a plain launch on `stream`; job.ncols == job.width, job.col0 == 0 (a device job);
@@ -212,5 +229,8 @@ struct PtV4Frames {
 //   kBatch   `scenes`, `frames`, and with an env term `envs`; job.env, env_w, env_h, frame_first and nframes
 //            are not read (the caller launches only when some view has frames)
 // Every kind but kViews runs the preparation kernel (pt_v4_scenes_prep_kernel) on the stream first.
+// `stats` (kBatch only, else hipErrorInvalidValue): the kind's statistics instances (kPtV4BatchStatsKeys), which
+// also add each view's statistics to stats->of_view; nullptr: the instances above.
 hipError_t pt_launch_v4_batched(PtV4BatchKind kind, const PtV4Job& job, const PtV4Scene* scene, const PtV4Views& views,
-                                const PtV4Scenes* scenes, const PtV4Envs* envs, const PtV4Frames* frames, hipStream_t stream);
+                                const PtV4Scenes* scenes, const PtV4Envs* envs, const PtV4Frames* frames, hipStream_t stream,
+                                const PtV4Stats* stats = nullptr);

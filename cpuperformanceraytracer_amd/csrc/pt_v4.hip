@@ -40,6 +40,7 @@
 #include "pt_chain.h"
 #include "pt_wave.h"
 #include "pt_tonemap.h"
+#include "pt_v4_stats.h"
 #include <algorithm>
 #include <cstring>
 #include <utility>
@@ -932,8 +933,9 @@ __device__ __forceinline__ void v4_present(const PtV4Job& job, int X, int Y, V3 
 template <int ENV, int LAYOUT, bool COUNT, bool DEF, int FEXP, bool DFL = false, bool PRESENT = false>
 __global__ __launch_bounds__(64 * kWaves) PT_V4_OCC void pt_v4_kernel(PtV4Job job, PtV4Scene sc)
 {
-    constexpr bool VIEWS = false, SCENES = false, ENVS = false, FRAMES = false;
+    constexpr bool VIEWS = false, SCENES = false, ENVS = false, FRAMES = false, STATS = false;
     constexpr PtV4Frames fa{nullptr};                  // (named in discarded statements only)
+    constexpr PtV4Stats sta{nullptr};                  // (likewise)
     constexpr PtV4Views va{nullptr, 0, nullptr, 0u};   // (named in discarded statements only)
     constexpr PtV4Scenes sa{nullptr, 0, nullptr};      // (likewise)
     constexpr PtV4Envs ea{nullptr, 0, nullptr};        // (likewise)
@@ -951,7 +953,9 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_views_kerne
 {
     static_assert(LAYOUT != PT_LAYOUT_TILED_PLANAR8, "views run the generic, uncounted row-layout form");
     constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = false, ENVS = false, FRAMES = false;
+    constexpr bool STATS = false;
     constexpr PtV4Frames fa{nullptr};               // (named in discarded statements only)
+    constexpr PtV4Stats sta{nullptr};               // (likewise)
     constexpr PtV4Scenes sa{nullptr, 0, nullptr};   // (named in discarded statements only)
     constexpr PtV4Envs ea{nullptr, 0, nullptr};     // (likewise)
     V4SceneRec srec;                                // (likewise)
@@ -968,7 +972,9 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_scenes_kern
 {
     static_assert(LAYOUT != PT_LAYOUT_TILED_PLANAR8, "scenes run the generic, uncounted row-layout form");
     constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = true, ENVS = false, FRAMES = false;
+    constexpr bool STATS = false;
     constexpr PtV4Frames fa{nullptr};             // (named in discarded statements only)
+    constexpr PtV4Stats sta{nullptr};             // (likewise)
     constexpr PtV4Scene sc{};   // (named in discarded statements only)
     constexpr PtV4Envs ea{nullptr, 0, nullptr};   // (likewise)
     V4ViewCam cam;      // the tile's view's camera
@@ -987,8 +993,10 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_envs_kernel
     static_assert(LAYOUT != PT_LAYOUT_TILED_PLANAR8, "envs run the generic, uncounted row-layout form");
     static_assert(ENV != PT_V4_ENV_NONE_, "an envs launch has an env term");
     constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = true, ENVS = true, FRAMES = false;
+    constexpr bool STATS = false;
     constexpr PtV4Scene sc{};   // (named in discarded statements only)
     constexpr PtV4Frames fa{nullptr};   // (likewise)
+    constexpr PtV4Stats sta{nullptr};   // (likewise)
     V4ViewCam cam;      // the tile's view's camera,
     V4SceneRec srec;    // its scene and (the pool's `tex`) its texture: all taken when the wave takes a tile
 #include "pt_v4_tile_pool.inc"
@@ -1005,10 +1013,28 @@ __global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_batch_kerne
 {
     static_assert(LAYOUT != PT_LAYOUT_TILED_PLANAR8, "batches run the generic, uncounted row-layout form");
     constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = true;
-    constexpr bool ENVS = ENV != PT_V4_ENV_NONE_, FRAMES = true;
+    constexpr bool ENVS = ENV != PT_V4_ENV_NONE_, FRAMES = true, STATS = false;
     constexpr PtV4Scene sc{};   // (named in discarded statements only)
+    constexpr PtV4Stats sta{nullptr};   // (likewise)
     V4ViewCam cam;      // the tile's view's camera,
     V4SceneRec srec;    // its scene, its texture (the pool's `tex`) and its frame range: all taken with the tile
+#include "pt_v4_tile_pool.inc"
+}
+
+// The batch kernel that also reports how much each view's displayed image moved (pt_v4_render_device_batch_stats,
+// pt_v4.h PtV4Stats): pt_v4_batch_kernel's text plus STATS -- the same 12 instances once more (pt_kernel_pick.h
+// kPtV4BatchStatsKeys), so the plain batch instances keep their code.  Everything it adds to the pool's body sits
+// under `if constexpr (STATS)`, at the tile's end: nothing of it is live in the pool loop.
+template <int ENV, int LAYOUT, int FEXP>
+__global__ __launch_bounds__(64 * kWaves) PT_V4_VIEWS_OCC void pt_v4_batch_stats_kernel(PtV4Job job, PtV4Views va, PtV4Scenes sa, PtV4Envs ea,
+                                                                                        PtV4Frames fa, PtV4Stats sta)
+{
+    static_assert(LAYOUT != PT_LAYOUT_TILED_PLANAR8, "batches run the generic, uncounted row-layout form");
+    constexpr bool VIEWS = true, COUNT = false, DEF = false, DFL = false, PRESENT = false, SCENES = true;
+    constexpr bool ENVS = ENV != PT_V4_ENV_NONE_, FRAMES = true, STATS = true;
+    constexpr PtV4Scene sc{};   // (named in discarded statements only)
+    V4ViewCam cam;      // the tile's view's camera,
+    V4SceneRec srec;    // its scene, its texture, its frame range and its statistics record: all follow the tile's view
 #include "pt_v4_tile_pool.inc"
 }
 
@@ -1552,6 +1578,17 @@ const V4BatchedTable<std::make_index_sequence<kPtV4BatchedKeyCount>> kV4BatchedT
 static_assert(kV4BatchedTable.matches, "the table holds the listed keys, in their order");
 PtResidentCache<kPtV4BatchedKeyCount> v4_batched_resident;
 
+// The batch kind's statistics instances: entry i is the kernel of kPtV4BatchStatsKeys[i], as above.
+template <typename Seq>
+struct V4BatchStatsTable;
+template <size_t... I>
+struct V4BatchStatsTable<std::index_sequence<I...>> {
+    const void* kern[sizeof...(I)] = {
+        (const void*)pt_v4_batch_stats_kernel<kPtV4BatchStatsKeys.k[I].env, kPtV4BatchStatsKeys.k[I].layout, kPtV4BatchStatsKeys.k[I].fexp>...};
+};
+const V4BatchStatsTable<std::make_index_sequence<kPtV4BatchStatsKeyCount>> kV4BatchStatsTable;
+PtResidentCache<kPtV4BatchStatsKeyCount> v4_batch_stats_resident;
+
 }  // namespace
 
 hipError_t pt_v4_set_chain_polls(uint32_t polls)
@@ -1603,7 +1640,7 @@ hipError_t pt_launch_v4(const PtV4Job& j_in, const PtV4Scene& sc, hipStream_t st
 }
 
 hipError_t pt_launch_v4_batched(PtV4BatchKind kind, const PtV4Job& j, const PtV4Scene* sc, const PtV4Views& va, const PtV4Scenes* sa,
-                                const PtV4Envs* ea, const PtV4Frames* fa, hipStream_t st)
+                                const PtV4Envs* ea, const PtV4Frames* fa, hipStream_t st, const PtV4Stats* sta)
 {
     const bool views = kind == PtV4BatchKind::kViews, batch = kind == PtV4BatchKind::kBatch;
     const bool env_term = j.env_mode != PT_V4_ENV_NONE_;
@@ -1617,12 +1654,16 @@ hipError_t pt_launch_v4_batched(PtV4BatchKind kind, const PtV4Job& j, const PtV4
     if (env_table ? !ea || !ea->table || ea->nenvs < 1 || !ea->env_of_view : env_term && (!j.env || j.env_w <= 0 || j.env_h <= 0))
         return hipErrorInvalidValue;
     if (batch && (!fa || !fa->range_of_view)) return hipErrorInvalidValue;
+    if (sta && (!batch || !sta->of_view)) return hipErrorInvalidValue;
     if (!j.queue || j.order || j.units || j.cost || j.counters) return hipErrorInvalidValue;   // unscheduled, uncounted
     if (!pt_pick_v4_batched_valid(kind, j.env_mode, j.layout)) return hipErrorInvalidValue;
     const uint64_t tiles = (uint64_t)((j.ncols + 7) / 8) * (uint64_t)((j.nrows + 7) / 8) * (uint64_t)va.nviews;
     if (tiles > PT_TILE_MASK) return hipErrorInvalidValue;   // (a queue entry carries view * tiles + tile)
-    const int i = kPtV4BatchedKeys.find(pt_pick_v4_batched_key(kind, j.env_mode, j.layout, j.fast_exp != 0));
-    const int r = i < 0 ? 0 : v4_batched_resident.get((size_t)i, kV4BatchedTable.kern[i], 64 * kWaves);
+    // the pick: the kind's key in its list -- with statistics, the batch kind's key in the statistics list
+    const PtV4BatchedKey key = pt_pick_v4_batched_key(kind, j.env_mode, j.layout, j.fast_exp != 0);
+    const int i = sta ? kPtV4BatchStatsKeys.find(key) : kPtV4BatchedKeys.find(key);
+    const void* const kern = i < 0 ? nullptr : sta ? kV4BatchStatsTable.kern[i] : kV4BatchedTable.kern[i];
+    const int r = i < 0 ? 0 : sta ? v4_batch_stats_resident.get((size_t)i, kern, 64 * kWaves) : v4_batched_resident.get((size_t)i, kern, 64 * kWaves);
     if (r <= 0) return i < 0 ? hipErrorInvalidValue : hipErrorInvalidDevice;
     uint32_t grid = pt_pick_grid((uint32_t)r, (uint32_t)tiles, kWaves);
     if (va.grid_cap && grid > va.grid_cap) grid = va.grid_cap;
@@ -1633,8 +1674,8 @@ hipError_t pt_launch_v4_batched(PtV4BatchKind kind, const PtV4Job& j, const PtV4
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    // the kernel's parameters, in its order: (job, scene, views) or (job, views, scenes[, envs[, frames]])
+    // the kernel's parameters, in its order: (job, scene, views) or (job, views, scenes[, envs[, frames[, stats]]])
     const PtV4Envs no_envs{nullptr, 0, nullptr};   // (a batch launch without an env term: not read)
-    const void* const args[5] = {&j, views ? (const void*)sc : &va, views ? (const void*)&va : sa, env_table ? ea : &no_envs, fa};
-    return hipLaunchKernel(kV4BatchedTable.kern[i], dim3(grid), dim3(64 * kWaves), const_cast<void**>(args), 0, st);
+    const void* const args[6] = {&j, views ? (const void*)sc : &va, views ? (const void*)&va : sa, env_table ? ea : &no_envs, fa, sta};
+    return hipLaunchKernel(kern, dim3(grid), dim3(64 * kWaves), const_cast<void**>(args), 0, st);
 }

@@ -1,8 +1,8 @@
 // pt_v4_tile_pool.inc -- the body of the v4 per-tile pool kernels (pt_v4.hip includes it inside
-// pt_v4_kernel, pt_v4_views_kernel, pt_v4_scenes_kernel, pt_v4_envs_kernel and pt_v4_batch_kernel, which
-// declare ENV, LAYOUT, COUNT, DEF, FEXP, DFL, PRESENT, VIEWS, SCENES, ENVS, FRAMES, the kernel arguments job
-// and sc, `cam`, the views arguments `va`, the scenes arguments `sa`, the view's scene `srec`, the envs
-// arguments `ea` and the frame ranges `fa`).
+// pt_v4_kernel, pt_v4_views_kernel, pt_v4_scenes_kernel, pt_v4_envs_kernel, pt_v4_batch_kernel and
+// pt_v4_batch_stats_kernel, which declare ENV, LAYOUT, COUNT, DEF, FEXP, DFL, PRESENT, VIEWS, SCENES, ENVS, FRAMES,
+// STATS, the kernel arguments job and sc, `cam`, the views arguments `va`, the scenes arguments `sa`, the view's
+// scene `srec`, the envs arguments `ea`, the frame ranges `fa` and the statistics records `sta`).
     // SCENES: no block-wide material table (each wave follows its own view's scene: srec.mat / srec.mx).
     // SLDS (the A/B build PT_V4_SCENES_LDS=1): a table per wave in LDS, refilled when the wave takes a tile,
     // paid for by a shorter env miss queue, so that the block stays within 25 LDS granules.
@@ -303,6 +303,26 @@
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     if ((FRAMES ? t_nframes : job.nframes) <= 0) next_tile = tq.next(job.err);   // no chunk ran
+    if constexpr (STATS) {
+        // How much the tile's displayed pixels moved (pt_v4.h PtV4Stats): each lane with a pixel packs the value
+        // the launch found -- re-read here, the slice is untouched until the store below, so no old value lives
+        // through the pool loop (and accumulate 0, which never loaded it, needs no other path) -- and the value it
+        // is about to store; the wave reduces one register (pt_v4_stats.h) and one lane adds the tile's sums to
+        // its view's record.  A lane without a pixel contributes 0.  The branch is wave-uniform (t_nframes is the
+        // view's, in a scalar register): a view of 0 frames issues nothing and its record stays as the host
+        // cleared it.
+        if (t_nframes > 0) {
+            uint32_t d = 0;
+            if (pvalid)
+                d = v4_stats_delta(pt_tone::pack<true, true>(acc_p[0], acc_p[cs], acc_p[2 * cs], true),
+                                   pt_tone::pack<true, true>(acc.x, acc.y, acc.z, true));
+            const uint32_t n_changed = (uint32_t)__builtin_popcountll(pt_ballot(d != 0u));
+            d = v4_stats_wave(d);
+            // (checked build: a record beyond the nviews records is reported and nothing added)
+            if (lane == 0 && PT_GUARD(job.err, view < (uint32_t)va.nviews, PT_G_STATS, view))
+                v4_stats_commit(sta.of_view + view, d & 0xffffu, n_changed, d >> 16);
+        }
+    }
     if (pvalid) {
         if (!FRAMES || t_nframes > 0) {
             acc_p[0] = acc.x;

@@ -418,14 +418,20 @@ def render_v4_device_batch(buf, cameras, width: int, height: int, *, frames=None
                            env_of_view=None, pixels=None, frame_first: int = 1, nframes: int = 0, num_bounces: int = 8,
                            row_start: int = 0, row_stride: int = 1, nrows: int | None = None,
                            layout: int = N.PT_LAYOUT_INTERLEAVED, use_env: bool | None = None,
-                           pixel_format: int = N.PT_PIXEL_RGBA8, stream=None) -> None:
+                           pixel_format: int = N.PT_PIXEL_RGBA8, stream=None, stats=None) -> None:
     """Everything per view in one launch (pt_v4_render_device_batch): render_v4_device_envs with a frame range
     per view.  `frames` is a sequence of (frame_first, nframes), one per camera -- a view of 0 frames keeps its
     slice of `buf` bit for bit and still gets its pixels -- or None: every view renders the keywords
     frame_first / nframes (which are not read otherwise).  `scenes` None: the current scene.  `envs` None: the
     map of set_env_map when use_env (None: "when a set is given"), else the ambient.  Slice v of `buf` ends bit
     for bit as that view's env map, scene, v4_camera(*cameras[v]) and render_v4_device over frames[v] would
-    leave it; no process-wide state is changed.  Asynchronous on `stream`."""
+    leave it; no process-wide state is changed.  Asynchronous on `stream`.
+
+    `stats` None: that call.  A contiguous int32 tensor of nviews x 4 on `buf`'s device: the same render through
+    pt_v4_render_device_batch_stats, which overwrites row v with view v's pt_v4_view_stats record -- how much the
+    view's 8-bit image (the v4_config's tonemap pair; R, G, B) moved in this launch: columns 0 and 1 are the low
+    and high word of sum_delta, column 2 is `changed`, column 3 is max_delta (v4_view_stats reads them).  A view
+    of 0 frames has zeros.  Read it after the stream reaches the call."""
     nrows = height if nrows is None else nrows
     cams = [(tuple(float(x) for x in pos), float(fov)) for pos, fov in cameras]
     nviews = len(cams)
@@ -469,7 +475,65 @@ def render_v4_device_batch(buf, cameras, width: int, height: int, *, frames=None
         b.env_of_view = emap
     b.pixels = pixels.data_ptr() if pixels is not None else None
     b.format = pixel_format
-    N.check(N.load().pt_v4_render_device_batch(ctypes.byref(job), ctypes.byref(b), _stream(stream)), "pt_v4_render_device_batch")
+    if stats is None:
+        N.check(N.load().pt_v4_render_device_batch(ctypes.byref(job), ctypes.byref(b), _stream(stream)), "pt_v4_render_device_batch")
+        return
+    import torch
+    if (not isinstance(stats, torch.Tensor) or stats.device != buf.device or stats.dtype != torch.int32 or
+            tuple(stats.shape) != (nviews, 4) or not stats.is_contiguous()):
+        raise N.PtError(N.PT_EINVAL, "render_v4_device_batch",
+                        f"stats must be a contiguous int32 tensor of {nviews} x 4 on the buffer's device")
+    N.check(N.load().pt_v4_render_device_batch_stats(ctypes.byref(job), ctypes.byref(b), stats.data_ptr(), _stream(stream)),
+            "pt_v4_render_device_batch_stats")
+
+
+def v4_view_stats(stats) -> list[dict]:
+    """The records of a `stats` tensor of render_v4_device_batch as [{sum_delta, changed, max_delta}], one per view.
+    It copies the tensor to the host, which waits for the work queued before on the current stream: nviews x 16
+    bytes."""
+    import numpy as np
+    a = np.ascontiguousarray(stats.cpu().numpy()).view(np.dtype([("sum_delta", "<u8"), ("changed", "<u4"), ("max_delta", "<u4")]))
+    return [{"sum_delta": int(r["sum_delta"]), "changed": int(r["changed"]), "max_delta": int(r["max_delta"])} for r in a.reshape(-1)]
+
+
+def render_v4_adaptive(buf, cameras, width: int, height: int, *, max_frames: int, frames_per_round: int = 8, tol: int = 0,
+                       patience: int = 1, **batch_kw) -> list[int]:
+    """Render every view until its displayed image stops moving, in rounds of one batch launch each; returns the
+    frames each view rendered.  Every view starts at frame 1 (the caller zeroes `buf` for a fresh image, or keeps
+    what is there to blend into).  Each round an active view gets min(frames_per_round, max_frames - done) frames
+    and a retired view 0 (its slice and pixels stay as they are); after the launch the nviews statistics records
+    are read back -- the only synchronisation, 16 bytes per view.  A view's quiet count goes up when its max_delta
+    <= tol and is reset to 0 otherwise; the view retires when the count reaches `patience`, or at max_frames.
+    `batch_kw`: the keywords of render_v4_device_batch but frames, frame_first, nframes and stats.
+
+    8-bit stability is a display criterion, not a variance bound: it says the picture on screen has stopped
+    changing at this frame count's blend factor (1 / (frame + 1) shrinks every round), not that the estimate's
+    error is below anything.  Use a larger `patience` where a view may rest for one round and move again."""
+    import torch
+    for k in ("frames", "frame_first", "nframes", "stats"):
+        if k in batch_kw:
+            raise N.PtError(N.PT_EINVAL, "render_v4_adaptive", f"the keyword {k} is the loop's own")
+    if max_frames < 0 or frames_per_round < 1 or patience < 1 or tol < 0:
+        raise N.PtError(N.PT_EINVAL, "render_v4_adaptive", "max_frames >= 0, frames_per_round >= 1, patience >= 1, tol >= 0")
+    cameras = list(cameras)
+    nviews = len(cameras)
+    done, quiet = [0] * nviews, [0] * nviews
+    active = [max_frames > 0] * nviews
+    stats = torch.zeros((nviews, 4), dtype=torch.int32, device=buf.device) if nviews else None
+    stream = batch_kw.get("stream")
+    while any(active):
+        frames = [(1 + done[v], min(frames_per_round, max_frames - done[v]) if active[v] else 0) for v in range(nviews)]
+        render_v4_device_batch(buf, cameras, width, height, frames=frames, stats=stats, **batch_kw)
+        if stream is not None:
+            stream.synchronize()
+        recs = v4_view_stats(stats)
+        for v in range(nviews):
+            if not active[v]:
+                continue
+            done[v] += frames[v][1]
+            quiet[v] = quiet[v] + 1 if recs[v]["max_delta"] <= tol else 0
+            active[v] = quiet[v] < patience and done[v] < max_frames
+    return done
 
 
 def count_v4_device(buf, width: int, height: int, *, frame_first: int, nframes: int, num_bounces: int = 8,

@@ -471,6 +471,34 @@ typedef struct pt_v4_batch {
     int32_t format;
 } pt_v4_batch;
 int pt_v4_render_device_batch(const pt_device_job* job, const pt_v4_batch* batch, void* hip_stream);
+/* The batch call that also says, per view, how much the DISPLAYED image moved: what a caller needs to decide
+ * which views have converged (frames[v].nframes = 0 from then on) without keeping, reading back or comparing
+ * pixels of its own.  Everything but `stats` is exactly pt_v4_render_device_batch -- the same accumulator and
+ * pixel slices bit for bit, the same checks before any GPU work, the same staging ring and asynchrony, a plain
+ * launch that ends a live chain, no process-wide state read or changed beyond what that call reads.
+ *   compared  `before` is the packed 8-bit value of the view's accumulator slice as the launch finds it --
+ *           pt_tonemap_device of the slice before the call, with pt_v4_config's fast_aces / fast_gamma --
+ *           and `after` the same of the slice as the launch leaves it.  Only R, G and B count (not the
+ *           alpha / X byte); the result depends neither on batch->format nor on batch->pixels being NULL.
+ *   stats   device memory on the job's device, nviews records in view order; NULL: PT_EINVAL.  Overwritten,
+ *           never accumulated: the library clears it on hip_stream before the launch.  Read it after the
+ *           stream reaches that point (16 bytes per view are the only thing a steering loop reads back).
+ *   A view of 0 frames has all-zero stats.  If every view has 0 frames, or nrows == 0: no render launch,
+ *           `stats` is still cleared on the stream, PT_OK.
+ *   Both values of pt_v4_config.accumulate_frames are supported (with 0 the old value is loaded for the
+ *           statistics only).  All three fields are integers combined by integer atomics (add, add, max):
+ *           the result does not depend on the order in which waves finish.
+ *   With the default tonemap pair (fast_aces 1, fast_gamma 1) the render kernel compares as it stores; any
+ *           other pair packs the old slices into library-owned scratch before the render and compares in the
+ *           pass that writes the pixels.
+ * 8-bit stability is a display criterion -- the picture on screen stopped changing -- not a variance bound. */
+typedef struct pt_v4_view_stats {   /* 16 bytes */
+    uint64_t sum_delta;   /* sum over the view's pixels and the channels R, G, B of |after - before| (8-bit values) */
+    uint32_t changed;     /* pixels whose packed R, G, B differ */
+    uint32_t max_delta;   /* largest |after - before| of any one channel, 0..255 */
+} pt_v4_view_stats;
+int pt_v4_render_device_batch_stats(const pt_device_job* job, const pt_v4_batch* batch, pt_v4_view_stats* stats,
+                                    void* hip_stream);
 int pt_v4_count_device(const pt_device_job* job, void* hip_stream, pt_work_counts* out);   /* sync */
 
 /* --- tile work queue: the host tile scheduler, on the GPU ------------------------

@@ -15,7 +15,16 @@ Each is timed with device events around the whole batch and with the host clock 
 scripts/bench_envs.py does; `--warmup` batches of each, then `--batches` (>= 20) of each, interleaved
 A/C/M/B; the median and the spread of each.  Before timing, A's accumulators are compared bit for bit with
 C's, and M's with B's.
-One JSON line on stdout; --out FILE also writes it there."""
+One JSON line on stdout; --out FILE also writes it there.
+
+--stats: the statistics leg instead (pt_v4_render_device_batch_stats), on A's inputs, interleaved A/S/P/Q/T:
+  A  the plain batch call, no pixels (the yardstick; with PT_MI355_LIB naming a library of an earlier revision
+     that lacks the statistics call, A alone is timed -- run the two alternately to compare revisions)
+  S  the statistics call, no pixels
+  P  the plain batch call writing pixels          Q  the statistics call writing pixels
+  T  what a caller does without it: pt_tonemap_device of all slices before, the plain call, pt_tonemap_device
+     after, and a torch reduction per view of the two pixel sets (sum, changed, max over R, G, B)
+Before timing, S's accumulators are compared bit for bit with A's and S's records with T's reduction."""
 from __future__ import annotations
 
 import argparse
@@ -77,6 +86,57 @@ class Lines:
     def m(self):
         N.check(self.L.pt_v4_render_device_batch(ctypes.byref(self.job["M"]), ctypes.byref(self.batch["M"]), self.st), "batch")
 
+    # ---- the statistics leg (--stats): all on buffer A / batch A ----
+    def stats_setup(self):
+        self.have_stats = hasattr(self.L, "pt_v4_render_device_batch_stats")
+        self.rec = torch.zeros((self.n, 4), dtype=torch.int32, device="cuda:0")
+        self.pix = torch.zeros((2, self.n, H, W), dtype=torch.int32, device="cuda:0")
+        self.batch["P"] = N.PtV4Batch()
+        ctypes.memmove(ctypes.byref(self.batch["P"]), ctypes.byref(self.batch["A"]), ctypes.sizeof(N.PtV4Batch))
+        self.batch["P"].pixels, self.batch["P"].format = self.pix[1].data_ptr(), N.PT_PIXEL_XRGB8
+
+    def s(self):
+        N.check(self.L.pt_v4_render_device_batch_stats(ctypes.byref(self.job["A"]), ctypes.byref(self.batch["A"]), self.rec.data_ptr(),
+                                                       self.st), "batch_stats")
+
+    def p(self):
+        N.check(self.L.pt_v4_render_device_batch(ctypes.byref(self.job["A"]), ctypes.byref(self.batch["P"]), self.st), "batch")
+
+    def q(self):
+        N.check(self.L.pt_v4_render_device_batch_stats(ctypes.byref(self.job["A"]), ctypes.byref(self.batch["P"]), self.rec.data_ptr(),
+                                                       self.st), "batch_stats")
+
+    def t(self):
+        tone = lambda k: N.check(self.L.pt_tonemap_device(self.bufs["A"].data_ptr(), W, self.n * H, N.PT_LAYOUT_INTERLEAVED, 0, 0,
+                                                          self.pix[k].data_ptr(), N.PT_PIXEL_XRGB8, self.st), "tonemap")
+        tone(0)
+        self.a()
+        tone(1)
+        ch = torch.stack([(self.pix >> sh) & 255 for sh in (16, 8, 0)], -1)   # 2 x n x H x W x 3
+        d = (ch[1] - ch[0]).abs().reshape(self.n, -1, 3)
+        self.t_rec = torch.stack([d.sum((1, 2)), (d.amax(2) > 0).sum(1), d.amax((1, 2))], 1)   # n x 3 int64
+
+    def run_stats(self, warmup, batches):
+        legs = [("A", self.a)] + ([("S", self.s), ("P", self.p), ("Q", self.q), ("T", self.t)] if self.have_stats else [])
+        rec = {k: [] for k, _ in legs}
+        for i in range(warmup + batches):
+            for name, fn in legs:
+                self.bufs["A"].zero_()   # (every leg renders frames 1..8 from zeros: the same work and the same records)
+                r = self.timed(fn)
+                if i >= warmup:
+                    rec[name].append(r)
+        out = {}
+        for name, r in rec.items():
+            dev, enq, tot = zip(*r)
+            out[name] = {"device_ms": stats(dev), "host_enqueue_ms": stats(enq), "host_total_ms": stats(tot)}
+        med = {k: out[k]["device_ms"]["median"] for k in out}
+        if self.have_stats:
+            out["S_over_A_device"] = med["S"] / med["A"]
+            out["Q_over_P_device"] = med["Q"] / med["P"]
+            out["T_over_A_device"] = med["T"] / med["A"]
+            out["T_over_S_device"] = med["T"] / med["S"]
+        return out
+
     def c(self):
         N.check(self.L.pt_v4_render_device_envs(ctypes.byref(self.job["C"]), self.envs.handle, None, None, 0, None, self.cams, self.n,
                                                 None, 0, self.st), "envs")
@@ -132,12 +192,15 @@ def main():
     ap.add_argument("--batches", type=int, default=24)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--stats", action="store_true", help="the statistics leg (see the module text)")
     args = ap.parse_args()
     pt.init(num_bounces=BOUNCES, device=0)
     pt.v4_config()
     pt.InitializeScene()
 
     lines = Lines(circle(args.views), [synthetic_env(ENV_H, ENV_W, 1000 + v) for v in range(args.views)])
+    if args.stats:
+        return main_stats(args, lines)
     for fn in (lines.a, lines.c, lines.m, lines.b):
         fn()
     torch.cuda.synchronize()
@@ -156,6 +219,40 @@ def main():
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text(line + "\n")
     return 0 if same_ac and same_mb else 1
+
+
+def main_stats(args, lines):
+    lines.stats_setup()
+    res = {"workload": {"views": args.views, "width": W, "height": H, "frames": FRAMES, "bounces": BOUNCES, "scene": "default",
+                        "envs": f"{args.views} synthetic equirect {ENV_W}x{ENV_H}", "start": "zeros, every timed call",
+                        "batches": args.batches, "warmup": args.warmup, "lib": str(N.lib_path().name)},
+           "has_stats_call": lines.have_stats}
+    ok = True
+    if lines.have_stats:
+        lines.a()
+        torch.cuda.synchronize()
+        plain = lines.bufs["A"].clone()
+        lines.bufs["A"].zero_()
+        lines.s()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(plain.view(torch.int32), lines.bufs["A"].view(torch.int32)))
+        got = lines.rec.cpu().numpy().view(np.dtype([("s", "<u8"), ("c", "<u4"), ("m", "<u4")])).reshape(-1)
+        lines.bufs["A"].zero_()
+        lines.t()
+        torch.cuda.synchronize()
+        want = lines.t_rec.cpu().numpy()
+        agree = bool((got["s"] == want[:, 0]).all() and (got["c"] == want[:, 1]).all() and (got["m"] == want[:, 2]).all())
+        res.update({"bit_equal_S_A": same, "records_equal_S_T": agree, "records_sum_delta_total": int(got["s"].sum())})
+        ok = same and agree
+    res["small"] = lines.run_stats(args.warmup, args.batches)
+    lines.envs.close()
+    pt.shutdown()
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(line + "\n")
+    return 0 if ok else 1
 
 
 if __name__ == "__main__":
