@@ -18,7 +18,10 @@
 // The containment is checked with the interval ends as computed here (fl(z -+ E)), so the rounding of
 // the ends is covered too.  The operations are f32 add / mul / fma and the correctly rounded 1/x, a/b
 // and sqrt (pt_exactmath.h on the GPU, bit-identical to IEEE inside the ranges used here), so host and
-// GPU compute the same bits and the host's exhaustive check is a check of the GPU's values.
+// GPU are meant to compute the same bits.  That is checked on the GPU, not assumed: the device compile
+// with the kernels' PT_EC_* substitutions gives the host compile's (certified, row, col) on in-domain
+// and deliberately out-of-domain directions (tests/native/devmath_probe.hip section "envcert",
+// tests/test_gpu_devmath.py), which is what carries the host's exhaustive check over to the GPU.
 // Directions outside the domain (a component below 2^-20 or above 2^20 in magnitude, |d.y| > 1 -
 // 2^-20, NaN) and cells whose ends disagree take the exact path (the caller's fallback).
 #pragma once

@@ -8,7 +8,9 @@
 // below restate those algorithms operation for operation; compiled without contraction
 // (-ffp-contract=off) and with IEEE '/' and sqrt they give the host's bit patterns on any IEEE
 // binary32 unit.  Checked on the host against glibc: asinf on every f32 in [-1, 1], atanf on every
-// non-negative f32, atan2f on 1e8 random pairs (tests/test_invtrig.py).
+// non-negative f32, atan2f on 1e8 random pairs (tests/test_invtrig.py).  The device compile, with the
+// kernels' PT_IT_DIV / PT_IT_SQRT substitutions, is compared with that host compile on the GPU itself
+// (tests/native/devmath_probe.hip section "invtrig", tests/test_gpu_devmath.py).
 #pragma once
 #include <stdint.h>
 
@@ -20,7 +22,7 @@
 #endif
 #endif
 // correctly rounded '/' and sqrt; a GPU includer may substitute cheaper exact forms
-// (pt_exactmath.h div_guarded / sqrt_guarded, bit-identical for every input)
+// (pt_exactmath.h div_guarded / sqrt_guarded, bit-identical for every input: tests/test_gpu_devmath.py)
 #ifndef PT_IT_DIV
 #define PT_IT_DIV(a, b) ((a) / (b))
 #endif

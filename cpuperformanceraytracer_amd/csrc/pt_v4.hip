@@ -83,21 +83,9 @@ __device__ __forceinline__ float min_ps(float a, float b) { return a < b ? a : b
 __device__ __forceinline__ float saturate(float x) { return min_ps(max_ps(x, 0.0f), 1.0f); }
 // correctly rounded 1/x and sqrt: the fast sequences of pt_exactmath.h inside their verified
 // ranges, IEEE outside (bit-identical to '1.0f / x' and sqrtf for every input)
-__device__ __forceinline__ float rcp(float x)   // rcp -> 1.f / x (mathlib.h:415)
-{
-    float r = pt::rcp_rn(x);
-    const float ax = __builtin_fabsf(x);
-    if (__builtin_expect(!(ax >= 0x1p-125f && ax <= 0x1p125f), 0)) r = 1.0f / x;
-    return r;
-}
-// 1.f / x for an x >= 0 (or NaN) that is provably <= 2^125: only the lower end of rcp_rn's range can
-// fail (0, denormals), one compare guards it
-__device__ __forceinline__ float rcp_nonneg(float x)
-{
-    float r = pt::rcp_rn(x);
-    if (__builtin_expect(!(x >= 0x1p-125f), 0)) r = pt::rcp_tiny_rn(x);   // 0, denormals, NaN
-    return r;
-}
+__device__ __forceinline__ float rcp(float x) { return pt::rcp_guarded(x); }   // rcp -> 1.f / x (mathlib.h:415)
+// 1.f / x for an x >= 0 (or NaN) that is provably <= 2^125
+__device__ __forceinline__ float rcp_nonneg(float x) { return pt::rcp_nonneg_guarded(x); }
 __device__ __forceinline__ float sqrt_(float x) { return pt::sqrt_guarded(x); }
 __device__ __forceinline__ V3 normalize(V3 v) { return v * rcp(sqrt_(dot(v, v))); }  // mathlib.h:759
 // normalize of a vector no longer than ~2 (unit vectors, their sums and lerps): sqrt(dot) <= 2^125

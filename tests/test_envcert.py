@@ -3,8 +3,9 @@ glibc restatements they fall back to (csrc/pt_invtrig.h): the polynomial angles'
 atanf_glibc for EVERY f32 q in [2^-40, 2^40] and asinf_glibc for every f32 in [0, 1 - 2^-20]
 (exhaustive), the atan2 sign glue holds on random domain pairs, and every certified cell of the v4
 random-jitter sampler and of the config-4 nearest sampler equals the exact pipeline's on random unit
-directions.  The GPU computes the same bits (f32 add/mul/fma, correctly rounded 1/x, a/b, sqrt), and
-the GPU env / v4 parity tests stay bit-exact against the oracle."""
+directions.  This is the host compile; the kernels' compile, with rcp_rn / div_rn / sqrt_rn for 1/x,
+a/b and sqrt, gives the same (certified, row, col) on the GPU, out-of-domain directions included
+(tests/test_gpu_devmath.py, section envcert)."""
 from __future__ import annotations
 
 import re

@@ -1,7 +1,8 @@
 """The product's atan2f / asinf (csrc/pt_invtrig.h, compiled here for the host) equal the host libm
 -- what the reference's EquirectangularTextureSample calls (texture.cpp:112) -- on every f32 of
-asinf's domain, every non-negative f32 for atanf, and 2e8 random atan2f pairs.  The device build
-runs the same f32 operations with IEEE '/' and sqrt (bit-exact GPU env-map tests)."""
+asinf's domain, every non-negative f32 for atanf, and 2e8 random atan2f pairs.  This is the host
+compile, with '/' and sqrtf.  The kernels' compile, with div_guarded / sqrt_guarded in their place,
+is compared with it on the GPU (tests/test_gpu_devmath.py, section invtrig)."""
 from __future__ import annotations
 
 import shutil

@@ -1,8 +1,9 @@
 """The product's glibc restatements (csrc/pt_libmf.h, compiled here for the host) equal the host
 libm's expf / powf -- what the oracle calls where the reference calls SVML exp_ps / pow_ps under
 USE_FAST_APPROXIMATE_EXP 0 / USE_FAST_APPROXIMATE_GAMMA 0 (global_preprocessor_flags.h:62,64).
-The device compiles the same header; its double ops (mul, add, fma) are IEEE on gfx950, so the GPU
-gives the same bits (confirmed end-to-end by tests/test_gpu_flags.py)."""
+This is the host compile.  The device compile (tables indexed at run time, one double -> float
+conversion at possibly denormal results) is compared with it on the GPU on the same sets:
+tests/test_gpu_devmath.py, sections exp and pow."""
 from __future__ import annotations
 
 import shutil

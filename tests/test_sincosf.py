@@ -1,8 +1,9 @@
 """The product's sin/cos (csrc/pt_sincosf.h, compiled here for the host) equals the host libm's
 sinf/cosf -- the functions the reference and the oracle call -- on EVERY f32 of the domain the
 path tracer uses, a = Randomf3201 * 2*pi in [0, 2*pi] (demofox_path_tracing_scalar.cpp:45).
-The device compiles the same header; its double ops (mul, fma) are IEEE on gfx950, so the GPU
-result is the same bit pattern (confirmed end-to-end by the bit-exact GPU parity tests)."""
+This is the host compile.  The device compile (which has a branch of its own for two polynomial
+constants) is compared with it on the GPU, on the same two ranges and both outputs:
+tests/test_gpu_devmath.py, section sincos."""
 from __future__ import annotations
 
 import shutil
