@@ -23,6 +23,7 @@
 #include "pt_launch_plan.h"
 #include "pt_output.h"
 #include "pt_v4.h"
+#include "pt_v4_batch.h"
 #include "../../include/pt_mi355.h"
 #include <math.h>
 #include <stdarg.h>
@@ -142,10 +143,8 @@ struct Dev {
     // only once that event has completed (the host waits for it -- four launches back, normally long
     // done).  So a block that an earlier asynchronous launch may still be reading, on this stream or
     // another, is never written, and no stream is made to wait for another.  The block holds what the
-    // launch's kind needs, in this order: its scene records, its view table, its view -> scene mapping,
-    // its view -> texture mapping, a one-record env table, its frame ranges (a views launch: the view
-    // table alone).  A block has the size its largest launch so far needed (a scene record is ~2 KiB:
-    // 1024 of them ~2 MiB), grown only after the slot's event completed.
+    // launch's kind needs (pt_v4_batch.h PtV4BatchLayout).  A block has the size its largest launch so far
+    // needed (a scene record is ~2 KiB: 1024 of them ~2 MiB), grown only after the slot's event completed.
     struct BatchSlot {
         unsigned char* host = nullptr;  // page-locked
         unsigned char* dev = nullptr;
@@ -287,8 +286,7 @@ int fail(int code, const char* fmt, ...)
         if (e_ != hipSuccess) return fail(PT_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-constexpr uint32_t kMaxFrame = 1u << 24;   // iFrame is an f32 counter: exact below 2^24
-constexpr int32_t kMaxDim = 1 << 24;        // pixel coordinates are f32 in mainImage: exact up to 2^24
+// (kMaxFrame, kMaxDim: pt_v4_batch.h)
 #if PT_DIAG
 constexpr int kCounterSlots = 32 + 4 * 65536 + 96 * 65536;   // + per-wave records, per-tile log
 #else
@@ -1517,16 +1515,15 @@ int v4_rebuild()
 
 // The sky window of the current (scene, camera) (pt_v4_skywin.h): host arithmetic, built on first use
 // after a scene edit or a camera change.  PT_MI355_V4_SKYWIN=0: no window (A/B timing, tests).
-void v4_sky_window_for(const PtV4SceneDesc& d, const float position[3], PtV4SkyWin* out)   // scene `d` seen from `position`
+bool v4_skywin_off()
 {
     static const bool off = getenv("PT_MI355_V4_SKYWIN") && !strcmp(getenv("PT_MI355_V4_SKYWIN"), "0");
-    if (off) *out = PtV4SkyWin{-1, {}};
-    else pt_v4_skywin_build(d.nquads, d.quad, d.nspheres, d.sphere, position, out);
+    return off;
 }
 
 void v4_sky_window_of(const float position[3], PtV4SkyWin* out)   // the current scene seen from `position`
 {
-    v4_sky_window_for(g.v4desc, position, out);
+    pt_v4_sky_window_for(v4_skywin_off(), g.v4desc, position, out);
 }
 
 const PtV4SkyWin& v4_sky_window()
@@ -1538,19 +1535,33 @@ const PtV4SkyWin& v4_sky_window()
     return g.v4sky;
 }
 
-// camera.Distance of InitializeCamera (v4 :1500): 1.0f / tanf(c_FOVDegrees * 0.5f * c_pi / 180.0f) in
-// f32, c_pi = 3.14159265359f (mathutils.h:5); glibc tanf for MSVC's float overload
-float v4_camera_distance(float fov_degrees)
-{
-    const float c_pi = 3.14159265359f;
-    return 1.0f / tanf(fov_degrees * 0.5f * c_pi / 180.0f);
-}
-
 int v4_ensure_scene()
 {
     if (g.v4_scene_ready) return PT_OK;
     pt_v4_default_scene_desc(&g.v4desc);   // InitializeGlobalRenderResources -> InitializeScene (v4 :1650-1654)
     return v4_rebuild();
+}
+
+// what a job takes from the pt_v4_config
+void v4_config_fields(PtV4Job* j)
+{
+    j->random_jitter = g.v4cfg.random_jitter;
+    j->rejection = g.v4cfg.rejection;
+    j->accumulate = g.v4cfg.accumulate_frames;   // ACCUMULATE_FRAMES (flags.h:60)
+    j->fast_exp = g.v4cfg.fast_exp;              // USE_FAST_APPROXIMATE_EXP (flags.h:64)
+}
+
+// what a job (PtJob, PtV4Job) takes from a device job: its rows, layout, frame range and bounces
+template <class Job>
+void device_job_fields(Job* j, const pt_device_job& dj)
+{
+    j->row_start = dj.row_start;
+    j->row_stride = dj.row_stride;
+    j->nrows = dj.nrows;
+    j->layout = dj.layout;
+    j->frame_first = dj.frame_first;
+    j->nframes = dj.nframes;
+    j->num_bounces = dj.num_bounces;
 }
 
 PtV4Job v4_job(float* buf, int32_t w, int32_t h)
@@ -1569,10 +1580,7 @@ PtV4Job v4_job(float* buf, int32_t w, int32_t h)
     j.nframes = 1;   // NUM_SAMPLES_PER_FRAME = 1: one frame per DemofoxRenderOptV4 call
     j.num_bounces = g.v4cfg.num_bounces;
     j.env_mode = PT_V4_ENV_NONE;
-    j.random_jitter = g.v4cfg.random_jitter;
-    j.rejection = g.v4cfg.rejection;
-    j.accumulate = g.v4cfg.accumulate_frames;   // ACCUMULATE_FRAMES (flags.h:60)
-    j.fast_exp = g.v4cfg.fast_exp;              // USE_FAST_APPROXIMATE_EXP (flags.h:64)
+    v4_config_fields(&j);
     memcpy(j.cam_pos, g.v4cam.position, sizeof(j.cam_pos));
     j.cam_dist = g.v4cam_dist;
     // the literal-geometry instances also carry the default camera as literals (pt_v4_camera_is_default)
@@ -2081,27 +2089,10 @@ int pt_release_buffer(const void* buf)
 
 static int device_job(const pt_device_job* dj, PtJob* j)
 {
-    if (!dj || !dj->buf) return fail(PT_EINVAL, "null device job/buffer");
-    if (dj->width <= 0 || dj->height <= 0 || dj->nrows < 0 || dj->row_stride <= 0 || dj->row_start < 0)
-        return fail(PT_EINVAL, "invalid device job geometry");
-    if (dj->width > kMaxDim || dj->height > kMaxDim)
-        return fail(PT_EINVAL, "image side > 2^24 (f32 pixel coordinates inexact)");
-    if (dj->nrows > 0 && dj->row_start + (int64_t)(dj->nrows - 1) * dj->row_stride >= dj->height)
-        return fail(PT_EINVAL, "row shard exceeds the image height");
-    if (dj->layout != PT_LAYOUT_INTERLEAVED && dj->layout != PT_LAYOUT_PLANAR8)
-        return fail(PT_EINVAL, "device jobs support the interleaved and planar8 layouts");
-    if (dj->layout == PT_LAYOUT_PLANAR8 && dj->width % 8) return fail(PT_EINVAL, "planar8 needs width % 8 == 0");
-    if (dj->frame_first < 1 || dj->nframes < 0 || (uint64_t)dj->frame_first + (uint64_t)dj->nframes > kMaxFrame)
-        return fail(PT_EINVAL, "frame range [%u, +%d) invalid", dj->frame_first, dj->nframes);
-    if (dj->num_bounces < 0 || dj->num_bounces > 1024) return fail(PT_EINVAL, "num_bounces out of range");
+    int rc;
+    if ((rc = pt_check_device_job(dj, fail))) return rc;   // (pt_v4_batch.h)
     *j = base_job(dj->buf, dj->width, dj->height);
-    j->row_start = dj->row_start;
-    j->row_stride = dj->row_stride;
-    j->nrows = dj->nrows;
-    j->layout = dj->layout;
-    j->frame_first = dj->frame_first;
-    j->nframes = dj->nframes;
-    j->num_bounces = dj->num_bounces;
+    device_job_fields(j, *dj);
     if (dj->use_env) {
         if (!g.have_env) return fail(PT_ESTATE, "use_env without an env map (pt_set_env_map)");
         j->env_w = g.env_w;
@@ -2493,30 +2484,12 @@ void pt_v4_default_camera(pt_v4_camera* c)
     c->fov_degrees = 90.0f;  // c_FOVDegrees, v4 :20
 }
 
-// The camera check of pt_v4_set_camera and of every view of pt_v4_render_device_views (view >= 0: the
-// message names it); *dist: camera.Distance.
-static int v4_check_camera(const pt_v4_camera* c, float* dist, int view)
-{
-    char who[32] = "";
-    if (view >= 0) snprintf(who, sizeof(who), "view %d: ", view);
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(c->position[k]) || std::fabs(c->position[k]) > 1024.0f)
-            return fail(PT_EINVAL, "%scamera position[%d] = %g is not finite or beyond +-1024", who, k, (double)c->position[k]);
-    if (!std::isfinite(c->fov_degrees) || !(c->fov_degrees > 0.0f && c->fov_degrees < 180.0f))
-        return fail(PT_EINVAL, "%sfov_degrees %g outside (0, 180)", who, (double)c->fov_degrees);
-    *dist = v4_camera_distance(c->fov_degrees);
-    if (!(std::isnormal(*dist) && *dist > 0.0f))
-        return fail(PT_EINVAL, "%sfov_degrees %g gives the camera distance %g, not a finite positive normal f32", who,
-                    (double)c->fov_degrees, (double)*dist);
-    return PT_OK;
-}
-
 int pt_v4_set_camera(const pt_v4_camera* c)
 {
     int rc;
     float dist = 0.0f;
     if (!c) return fail(PT_EINVAL, "null v4 camera");
-    if ((rc = v4_check_camera(c, &dist, -1))) return rc;
+    if ((rc = pt_v4_check_camera(c, &dist, -1, fail))) return rc;   // (pt_v4_batch.h)
     g.v4cam = *c;
     g.v4cam_dist = dist;
     g.v4sky_ready = false;
@@ -2635,13 +2608,7 @@ static int v4_device_job(const pt_device_job* dj, PtV4Job* j4)
     PtJob j;
     if ((rc = device_job(&geo, &j)) || (rc = v4_ensure_scene())) return rc;
     *j4 = v4_job(dj->buf, dj->width, dj->height);
-    j4->row_start = dj->row_start;
-    j4->row_stride = dj->row_stride;
-    j4->nrows = dj->nrows;
-    j4->layout = dj->layout;
-    j4->frame_first = dj->frame_first;
-    j4->nframes = dj->nframes;
-    j4->num_bounces = dj->num_bounces;
+    device_job_fields(j4, *dj);
     if (dj->use_env) {
         if (g.v4cfg.env_mode == PT_V4_ENV_NONE) return fail(PT_ESTATE, "use_env with v4 env mode NONE");
         if ((rc = v4_use_env(*j4))) return rc;
@@ -2709,31 +2676,15 @@ int pt_v4_get_scene_desc(pt_v4_scene_desc* out)
     return PT_OK;
 }
 
-// The batched v4 launches (include/pt_mi355.h; pt_v4.h PtV4Views ... PtV4Frames).  Everything is checked
-// before the first HIP call.  The launch is a plain, unscheduled one of the kind's instances
-// (pt_launch_v4_batched) -- it joins (ends) a live chain and takes a tile-queue ring slot like every plain
-// launch, and touches no geometry's schedule state.  What the kernel reads per view travels in one block of
-// the device's batch ring (Dev::batch).
-// The four public calls are one function: `kind` says which call it is, and the arguments travel as a
-// pt_v4_batch (the views, scenes and envs calls fill one; they leave `frames` NULL and never read it).
-//   kViews  (pt_v4_render_device_views): a camera per view.  Every view renders the current process-wide
-//           scene, a kernel argument (g.v4scene), with the window of (that scene, its camera); the block is
-//           the view table alone.
-//   kScenes (pt_v4_render_device_scenes): the scene per view as well.  Nothing of the process-wide scene,
-//           camera or frame counter is read or written (the job is made from the arguments and the
-//           pt_v4_config alone).  Each record is pt_v4_build_scene of its description -- the code behind
-//           pt_v4_add_* -- and each view's window pt_v4_skywin_build of (its scene, its camera).  Records,
-//           view table and mapping travel in the block.
-//   kEnvs   (pt_v4_render_device_envs): the texture per view as well -- view v reads record env_of_view[v]
-//           of the env set's device table; the mapping travels at the end of the same block.  Then `scenes`
-//           may be NULL: every view renders the current process-wide scene (the one thing of the
-//           process-wide state read).
-//   kBatch  (pt_v4_render_device_batch): the frame range per view as well -- `frames`, or the job's range
-//           for every view when it is NULL -- in a parallel array at the end of the same block, and the
-//           batch instances, which read nothing but that array for first frame and count.  A texture per
-//           view when `envs` is given; without a set but with an env term, the process-wide map travels as
-//           a one-record table in the block (with a mapping of zeros), so that the kernel reads a table
-//           either way.
+// The batched v4 launches (include/pt_mi355.h; pt_v4.h PtV4Views ... PtV4Frames).  The four public calls are
+// one function: `kind` says which call it is, and the arguments travel as a pt_v4_batch (the views, scenes and
+// envs calls fill one; they leave `frames` NULL and never read it).  What a kind reads, where that lies in the
+// block of the device's batch ring (Dev::batch), every check -- all made before the first HIP call -- and the
+// block's contents are pt_v4_batch.h's; here is the sequence around them.  The launch is a plain, unscheduled
+// one of the kind's instances (pt_launch_v4_batched) -- it joins (ends) a live chain and takes a tile-queue ring
+// slot like every plain launch, and touches no geometry's schedule state.  Of the process-wide scene, camera and
+// frame counter only the scene is read, by a views launch (a kernel argument, g.v4scene) and by an envs or batch
+// launch without `scenes`: the job is made from the arguments and the pt_v4_config alone.
 //   `stats` (pt_v4_render_device_batch_stats; kBatch only): the same call, which also leaves each view's
 //           statistics in `stats` -- cleared on the stream first, also when nothing renders.  Under the default
 //           tonemap pair the batch kind's statistics instances compare as they store (pt_v4.h PtV4Stats); under
@@ -2757,153 +2708,42 @@ static int v4_stats_clear_only(const pt_device_job* dj, pt_v4_view_stats* stats,
     return PT_OK;
 }
 
-static int v4_batched_launch(const pt_device_job* dj, V4BatchKind kind, const pt_v4_batch& args, void* stream,
-                             pt_v4_view_stats* stats = nullptr)
+// The job of a batched launch: v4_device_job's without the process-wide camera (the views' records carry the
+// cameras and the windows) -- the arguments and the config.
+static int v4_batch_job(const pt_device_job& dj, const PtV4BatchShape& shape, PtV4Job* out)
 {
-    const bool views = kind == V4BatchKind::kViews, batch = kind == V4BatchKind::kBatch;
-    const bool with_envs = kind == V4BatchKind::kEnvs || (batch && args.envs);   // a texture per view, from an env set
-    const pt_v4_camera* const cams = args.cams;
-    const int32_t nviews = args.nviews;
-    const pt_v4_frame_range* const frames = batch ? args.frames : nullptr;
-    const pt_v4_scene_desc* scenes = args.scenes;
-    int32_t nscenes = args.nscenes;
-    const int32_t* const scene_of_view = args.scene_of_view;
-    const pt_v4_env_set* const envs = args.envs;
-    const int32_t* const env_of_view = args.env_of_view;
-    uint32_t* const pixels = args.pixels;
-    const int32_t format = args.format;
     int rc;
-    if (!dj) return fail(PT_EINVAL, "null device job");
-    {
-        pt_device_job geo = *dj;   // (the geometry / frame checks, as v4_device_job's)
-        geo.use_env = 0;
-        if (batch && frames) {     // (the job's own range is not read: each view's is checked below)
-            geo.frame_first = 1;
-            geo.nframes = 0;
-        }
-        PtJob unused;
-        if ((rc = device_job(&geo, &unused))) return rc;
-    }
-    if (!cams) return fail(PT_EINVAL, "null camera array");
-    if (nviews < 1 || nviews > PT_V4_MAX_VIEWS) return fail(PT_EINVAL, "nviews %d outside [1, %d]", nviews, PT_V4_MAX_VIEWS);
-    if (pixels && format != PT_PIXEL_RGBA8 && format != PT_PIXEL_XRGB8) return fail(PT_EINVAL, "unknown pixel format %d", format);
-    const uint64_t view_tiles = (uint64_t)((dj->width + 7) / 8) * (uint64_t)((dj->nrows + 7) / 8);
-    if (view_tiles * (uint64_t)nviews > PT_TILE_MASK)
-        return fail(PT_EINVAL, "%d views x %llu tiles exceed the tile queue's %u entries", nviews, (unsigned long long)view_tiles,
-                    PT_TILE_MASK);
-    std::vector<float> dist((size_t)nviews);
-    for (int32_t v = 0; v < nviews; ++v)
-        if ((rc = v4_check_camera(&cams[v], &dist[(size_t)v], v))) return rc;
-    const bool current_scene = (with_envs || batch) && !scenes;
-    if (current_scene) {
-        if (nscenes != 0 || scene_of_view) return fail(PT_EINVAL, "no scenes (the current scene): nscenes must be 0 and scene_of_view NULL");
-        if ((rc = v4_ensure_scene())) return rc;   // (host only)
-        scenes = reinterpret_cast<const pt_v4_scene_desc*>(&g.v4desc);
-        nscenes = 1;
-    }
-    if (!views) {   // (a views launch has no records: nscenes stays 0)
-        if (!scenes) return fail(PT_EINVAL, "null scene array");
-        if (nscenes < 1 || nscenes > PT_V4_MAX_VIEWS) return fail(PT_EINVAL, "nscenes %d outside [1, %d]", nscenes, PT_V4_MAX_VIEWS);
-        if (!scene_of_view && !current_scene && nscenes != nviews)
-            return fail(PT_EINVAL, "no scene_of_view: view v uses scene v, but nscenes %d != nviews %d", nscenes, nviews);
-        if (scene_of_view)
-            for (int32_t v = 0; v < nviews; ++v)
-                if (scene_of_view[v] < 0 || scene_of_view[v] >= nscenes)
-                    return fail(PT_EINVAL, "view %d: scene_of_view %d outside [0, %d)", v, scene_of_view[v], nscenes);
-    }
-    const PtV4SceneDesc* const desc = reinterpret_cast<const PtV4SceneDesc*>(scenes);
-    for (int32_t s = 0; s < nscenes; ++s) {
-        const PtV4SceneDesc& d = desc[s];
-        if (d.nquads < 0 || d.nspheres < 0 || d.nmat < 0 || d.nquads > PT_V4_MAX_OBJECTS || d.nspheres > PT_V4_MAX_OBJECTS ||
-            d.nquads + d.nspheres > PT_V4_MAX_OBJECTS || d.nmat > PT_V4_MAX_OBJECTS)
-            return fail(PT_EINVAL, "scene %d: %d quads + %d spheres, %d materials (each count >= 0; objects and materials <= %d)", s,
-                        d.nquads, d.nspheres, d.nmat, PT_V4_MAX_OBJECTS);
-    }
-    if (batch && envs && (!dj->use_env || g.v4cfg.env_mode == PT_V4_ENV_NONE))   // (before the set is looked at)
-        return fail(PT_EINVAL, "an env set needs an env term: use_env %d, v4 env mode %d", dj->use_env, g.v4cfg.env_mode);
-    if (with_envs) {
-        if (!envs) return fail(PT_EINVAL, "null env set");
-        if (!env_set_live(envs)) return fail(PT_EINVAL, "not a live env set (freed, or from before pt_shutdown)");
-        if (!env_of_view && envs->count != nviews)
-            return fail(PT_EINVAL, "no env_of_view: view v uses texture v, but the set has %d textures for %d views", envs->count, nviews);
-        if (env_of_view)
-            for (int32_t v = 0; v < nviews; ++v)
-                if (env_of_view[v] < 0 || env_of_view[v] >= envs->count)
-                    return fail(PT_EINVAL, "view %d: env_of_view %d outside [0, %d)", v, env_of_view[v], envs->count);
-        if (!dj->use_env || g.v4cfg.env_mode == PT_V4_ENV_NONE)
-            return fail(PT_EINVAL, "an envs launch needs an env term: use_env %d, v4 env mode %d", dj->use_env, g.v4cfg.env_mode);
-    }
-    if (batch) {
-        if (!envs && env_of_view) return fail(PT_EINVAL, "no env set (the process-wide env map, or none): env_of_view must be NULL");
-        bool any = false;
-        for (int32_t v = 0; v < nviews; ++v) {
-            const pt_v4_frame_range r = frames ? frames[v] : pt_v4_frame_range{dj->frame_first, dj->nframes};
-            if (r.frame_first < 1 || r.nframes < 0 || (uint64_t)r.frame_first + (uint64_t)r.nframes > kMaxFrame)
-                return fail(PT_EINVAL, "view %d: frame range [%u, +%d) invalid", v, r.frame_first, r.nframes);
-            any = any || r.nframes > 0;
-        }
-        if (!any || dj->nrows == 0) return stats ? v4_stats_clear_only(dj, stats, nviews, stream) : PT_OK;   // nothing to render
-    } else if (dj->nframes == 0 || dj->nrows == 0) {
-        return PT_OK;   // nothing to render
-    }
-
-    Dev* dvp = nullptr;
-    DeviceGuard guard;
-    if ((rc = ensure_init()) || (views && (rc = v4_ensure_scene()))) return rc;
-    // the job of v4_device_job without the process-wide camera: the arguments and the config
     PtV4Job j{};
-    j.buf = dj->buf;
-    j.width = dj->width;
-    j.height = dj->height;
+    j.buf = dj.buf;
+    j.width = dj.width;
+    j.height = dj.height;
     j.col0 = 0;
-    j.ncols = dj->width;
-    j.row_start = dj->row_start;
-    j.row_stride = dj->row_stride;
-    j.nrows = dj->nrows;
-    j.layout = dj->layout;
-    j.frame_first = dj->frame_first;
-    j.nframes = dj->nframes;
-    j.num_bounces = dj->num_bounces;
+    j.ncols = dj.width;
+    device_job_fields(&j, dj);
     j.env_mode = PT_V4_ENV_NONE;
-    j.random_jitter = g.v4cfg.random_jitter;
-    j.rejection = g.v4cfg.rejection;
-    j.accumulate = g.v4cfg.accumulate_frames;
-    j.fast_exp = g.v4cfg.fast_exp;
-    j.sky = PtV4SkyWin{-1, {}};   // (the views' records carry the cameras and the windows)
-    if (with_envs) {
+    v4_config_fields(&j);
+    j.sky = PtV4SkyWin{-1, {}};
+    if (shape.env_set()) {
         j.env_mode = g.v4cfg.env_mode;   // (job.env, env_w, env_h stay null: the views' records carry the textures)
-    } else if (batch) {
+    } else if (shape.frames) {
         // use_env 0 or env mode NONE: the ambient; else pt_set_env_map's texture as the one record of a staged table
-        if (dj->use_env && (rc = v4_use_env(j))) return rc;
-    } else if (dj->use_env) {
+        if (dj.use_env && (rc = v4_use_env(j))) return rc;
+    } else if (dj.use_env) {
         if (g.v4cfg.env_mode == PT_V4_ENV_NONE) return fail(PT_ESTATE, "use_env with v4 env mode NONE");
         if ((rc = v4_use_env(j))) return rc;
     }
-    if ((rc = dev_of(dj->buf, &dvp)) || (rc = use_dev(*dvp))) return rc;
-    Dev& dv = *dvp;
-    if (with_envs && envs->dev != dvp)
-        return fail(PT_EINVAL, "the env set lives on device %d, the job's buffer on device %d", envs->dev->ordinal, dv.ordinal);
-    hipStream_t st = (hipStream_t)stream;
-    if (!with_envs && j.env_mode != PT_V4_ENV_NONE) j.env = dv.denv;
-    j.err = dv.derr;
-    // the render kernel writes the pixels with the default tonemap pair; any other pair: a second pass
-    const bool fused = pixels && g.v4cfg.fast_aces && g.v4cfg.fast_gamma;
-    j.pix_xrgb = format == PT_PIXEL_XRGB8;
-    // and so with the statistics: compared in the render kernel, or (any other pair) around it
-    const bool stats_fused = stats && g.v4cfg.fast_aces && g.v4cfg.fast_gamma, stats_pass = stats && !stats_fused;
-    if (stats) HIP_TRY(hipMemsetAsync(stats, 0, (size_t)nviews * sizeof(pt_v4_view_stats), st));
+    *out = j;
+    return PT_OK;
+}
 
-    const auto up16 = [](size_t n) { return (n + 15u) & ~(size_t)15u; };
-    const size_t off_views = up16((size_t)nscenes * sizeof(PtV4SceneRec));
-    const size_t off_map = off_views + up16((size_t)nviews * sizeof(PtV4View));
-    const size_t off_emap = off_map + (views ? 0u : up16((size_t)nviews * sizeof(int32_t)));
-    const bool staged_env = batch && !with_envs && j.env_mode != PT_V4_ENV_NONE;
-    const size_t off_erec = off_emap + (with_envs || staged_env ? up16((size_t)nviews * sizeof(int32_t)) : 0u);
-    const size_t off_frames = off_erec + (staged_env ? up16(sizeof(PtV4EnvRec)) : 0u);
-    const size_t need = off_frames + (batch ? up16((size_t)nviews * sizeof(PtV4FrameRange)) : 0u);
+// The next slot of the device's batch ring, free to be written: its previous launch (kViewRing launches back) has
+// finished, its block holds `need` bytes and its statistics scratch `scratch_px` pixels (0: none wanted).  The
+// ring's cursor advances whether or not the slot can be had.
+static int batch_slot_acquire(Dev& dv, size_t need, size_t scratch_px, Dev::BatchSlot** out)
+{
     Dev::BatchSlot& ss = dv.batch[dv.batch_next++ % kViewRing];
     if (!ss.done) HIP_TRY(hipEventCreateWithFlags(&ss.done, hipEventDisableTiming));
-    if (ss.pending) {   // the slot's previous launch (kViewRing launches back) still reads the block: wait for it
+    if (ss.pending) {   // the slot's previous launch still reads the block: wait for it
         HIP_TRY(hipEventSynchronize(ss.done));
         ss.pending = false;
     }
@@ -2924,51 +2764,72 @@ static int v4_batched_launch(const pt_device_job* dj, V4BatchKind kind, const pt
         }
         ss.cap = cap;
     }
-    const size_t npix = (size_t)nviews * (size_t)dj->nrows * (size_t)dj->width;
-    if (stats_pass && ss.before_cap < npix) {   // (likewise: no launch reads the slot's scratch now)
+    if (ss.before_cap < scratch_px) {   // (likewise: no launch reads the slot's scratch now)
         if (ss.before) (void)hipFree(ss.before);
         ss.before = nullptr;
         ss.before_cap = 0;
-        if (hipMalloc((void**)&ss.before, npix * sizeof(uint32_t)) != hipSuccess) {
+        if (hipMalloc((void**)&ss.before, scratch_px * sizeof(uint32_t)) != hipSuccess) {
             ss.before = nullptr;
-            return fail(PT_ENOMEM, "hipMalloc(batch statistics scratch, %zu bytes) failed", npix * sizeof(uint32_t));
+            return fail(PT_ENOMEM, "hipMalloc(batch statistics scratch, %zu bytes) failed", scratch_px * sizeof(uint32_t));
         }
-        ss.before_cap = npix;
+        ss.before_cap = scratch_px;
     }
-    PtV4SceneRec* const hrec = reinterpret_cast<PtV4SceneRec*>(ss.host);
-    PtV4View* const hview = reinterpret_cast<PtV4View*>(ss.host + off_views);
-    int32_t* const hmap = reinterpret_cast<int32_t*>(ss.host + off_map);
-    for (int32_t s = 0; s < nscenes; ++s) {
-        if (pt_v4_build_scene(&desc[s], &hrec[s].sc)) return fail(PT_EINVAL, "scene %d exceeds MAX_OBJECTS", s);   // (checked above)
-        memset(hrec[s].mx, 0, sizeof(hrec[s].mx));   // (the preparation kernel fills them on the device)
-    }
-    for (int32_t v = 0; v < nviews; ++v) {
-        const int32_t s = scene_of_view ? scene_of_view[v] : current_scene ? 0 : v;
-        if (!views) hmap[v] = s;
-        if (with_envs) reinterpret_cast<int32_t*>(ss.host + off_emap)[v] = env_of_view ? env_of_view[v] : v;
-        if (staged_env) reinterpret_cast<int32_t*>(ss.host + off_emap)[v] = 0;
-        if (batch)
-            reinterpret_cast<PtV4FrameRange*>(ss.host + off_frames)[v] =
-                frames ? PtV4FrameRange{frames[v].frame_first, frames[v].nframes} : PtV4FrameRange{dj->frame_first, dj->nframes};
-        PtV4View& r = hview[v];
-        memcpy(r.cam_pos, cams[v].position, sizeof(r.cam_pos));
-        r.cam_dist = dist[(size_t)v];
-        v4_sky_window_for(views ? g.v4desc : desc[s], cams[v].position, &r.sky);
-    }
-    if (staged_env) *reinterpret_cast<PtV4EnvRec*>(ss.host + off_erec) = PtV4EnvRec{dv.denv, j.env_w, j.env_h};
-    HIP_TRY(hipMemcpyAsync(ss.dev, ss.host, need, hipMemcpyHostToDevice, st));
+    *out = &ss;
+    return PT_OK;
+}
+
+static int v4_batched_launch(const pt_device_job* dj, V4BatchKind kind, const pt_v4_batch& args, void* stream,
+                             pt_v4_view_stats* stats = nullptr)
+{
+    int rc;
+    const bool views = kind == V4BatchKind::kViews;
+    const PtV4BatchShape shape = pt_v4_batch_shape(kind, args, dj ? dj->use_env : 0, g.v4cfg.env_mode);
+    if (shape.current_scene && (rc = v4_ensure_scene())) return rc;   // (host only)
+    const pt_v4_env_set* const envs = shape.env_set() ? args.envs : nullptr;
+    const bool live = envs && env_set_live(envs);
+    const PtV4BatchState state{g.v4cfg.env_mode, live, live ? envs->count : 0, &g.v4desc, v4_skywin_off()};
+    std::vector<float> dist;
+    bool nothing = false;
+    if ((rc = pt_v4_batch_check(dj, shape, args, state, &dist, &nothing, fail))) return rc;
+    const int32_t nviews = args.nviews, nscenes = pt_v4_batch_nscenes(shape, args);
+    if (nothing) return stats ? v4_stats_clear_only(dj, stats, nviews, stream) : PT_OK;
+
+    Dev* dvp = nullptr;
+    DeviceGuard guard;
+    PtV4Job j;
+    if ((rc = ensure_init()) || (views && (rc = v4_ensure_scene())) || (rc = v4_batch_job(*dj, shape, &j))) return rc;
+    if ((rc = dev_of(dj->buf, &dvp)) || (rc = use_dev(*dvp))) return rc;
+    Dev& dv = *dvp;
+    if (envs && envs->dev != dvp)
+        return fail(PT_EINVAL, "the env set lives on device %d, the job's buffer on device %d", envs->dev->ordinal, dv.ordinal);
+    hipStream_t st = (hipStream_t)stream;
+    if (!envs && j.env_mode != PT_V4_ENV_NONE) j.env = dv.denv;
+    j.err = dv.derr;
+    // the render kernel writes the pixels with the default tonemap pair; any other pair: a second pass
+    const bool fused = args.pixels && g.v4cfg.fast_aces && g.v4cfg.fast_gamma;
+    j.pix_xrgb = args.format == PT_PIXEL_XRGB8;
+    // and so with the statistics: compared in the render kernel, or (any other pair) around it
+    const bool stats_fused = stats && g.v4cfg.fast_aces && g.v4cfg.fast_gamma, stats_pass = stats && !stats_fused;
+    if (stats) HIP_TRY(hipMemsetAsync(stats, 0, (size_t)nviews * sizeof(pt_v4_view_stats), st));
+
+    const PtV4BatchLayout lay = pt_v4_batch_layout(shape, nscenes, nviews);
+    Dev::BatchSlot* ssp = nullptr;
+    if ((rc = batch_slot_acquire(dv, lay.need, stats_pass ? (size_t)nviews * (size_t)dj->nrows * (size_t)dj->width : 0u, &ssp))) return rc;
+    Dev::BatchSlot& ss = *ssp;
+    if ((rc = pt_v4_batch_fill(ss.host, lay, shape, *dj, args, state, dist.data(), PtV4EnvRec{dv.denv, j.env_w, j.env_h}, fail))) return rc;
+    HIP_TRY(hipMemcpyAsync(ss.dev, ss.host, lay.need, hipMemcpyHostToDevice, st));
 
     LaunchSched ls;
     if ((rc = chain_join(dv, st)) || (rc = use_queue_slot(dv, st, &ls))) return rc;
     j.queue = ls.queue;
     j.queue_next = ls.queue_next;
-    const PtV4Views va{reinterpret_cast<const PtV4View*>(ss.dev + off_views), nviews, fused ? pixels : nullptr, g.v4_views_grid};
-    const PtV4Scenes sa{reinterpret_cast<PtV4SceneRec*>(ss.dev), nscenes, reinterpret_cast<const int32_t*>(ss.dev + off_map)};
-    const int32_t* const emap = reinterpret_cast<const int32_t*>(ss.dev + off_emap);
-    const PtV4Envs ea = with_envs    ? PtV4Envs{envs->table, envs->count, emap}
-                        : staged_env ? PtV4Envs{reinterpret_cast<const PtV4EnvRec*>(ss.dev + off_erec), 1, emap}
-                                     : PtV4Envs{nullptr, 0, nullptr};
-    const PtV4Frames fa{reinterpret_cast<const PtV4FrameRange*>(ss.dev + off_frames)};
+    const PtV4Views va{pt_v4_batch_views(ss.dev, lay), nviews, fused ? args.pixels : nullptr, g.v4_views_grid};
+    const PtV4Scenes sa{pt_v4_batch_scenes(ss.dev, lay), nscenes, pt_v4_batch_scene_map(ss.dev, lay)};
+    const int32_t* const emap = pt_v4_batch_env_map(ss.dev, lay);
+    const PtV4Envs ea = envs               ? PtV4Envs{envs->table, envs->count, emap}
+                        : shape.staged_env ? PtV4Envs{pt_v4_batch_env_rec(ss.dev, lay), 1, emap}
+                                           : PtV4Envs{nullptr, 0, nullptr};
+    const PtV4Frames fa{pt_v4_batch_frames(ss.dev, lay)};
     hipError_t e;
     if (stats_pass) {
         // the old slices as the display would show them, before the render overwrites them (after chain_join: a
@@ -2979,16 +2840,18 @@ static int v4_batched_launch(const pt_device_job* dj, V4BatchKind kind, const pt
     const PtV4Stats sta{reinterpret_cast<PtV4ViewStats*>(stats)};
     // (what the kind does not read is not passed; a views launch renders the process-wide scene)
     e = pt_launch_v4_batched(kind, j, views ? &g.v4scene : nullptr, va, views ? nullptr : &sa, ea.table ? &ea : nullptr,
-                             batch ? &fa : nullptr, st, stats_fused ? &sta : nullptr);
-    if (e != hipSuccess)
-        return fail(PT_EHIP, "v4 %s launch failed: %s", views ? "views" : batch ? "batch" : with_envs ? "envs" : "scenes", hipGetErrorString(e));
+                             shape.frames ? &fa : nullptr, st, stats_fused ? &sta : nullptr);
+    if (e != hipSuccess) {
+        static const char* const name[] = {"views", "scenes", "envs", "batch"};   // (PtV4BatchKind's order)
+        return fail(PT_EHIP, "v4 %s launch failed: %s", name[(int)kind], hipGetErrorString(e));
+    }
     HIP_TRY(hipEventRecord(ss.done, st));
     ss.pending = true;
     if ((rc = queue_done(dv, ls.slot, st, true))) return rc;
     if (stats_pass) {
         // the new slices against the scratch, per view; it writes the pixels too, so no conversion pass follows
         PtStatsJob sj{};
-        sj.tone = tone_job(j.buf, j.ncols, j.nrows, j.layout, 0, 0, pixels, format);
+        sj.tone = tone_job(j.buf, j.ncols, j.nrows, j.layout, 0, 0, args.pixels, args.format);
         sj.nviews = nviews;
         sj.before = ss.before;
         sj.ranges = fa.range_of_view;
@@ -2997,15 +2860,14 @@ static int v4_batched_launch(const pt_device_job* dj, V4BatchKind kind, const pt
         e = pt_launch_tonemap_stats(sj, st);
         if (e != hipSuccess) return fail(PT_EHIP, "statistics pass launch failed: %s", hipGetErrorString(e));
         HIP_TRY(hipEventRecord(ss.done, st));   // (again: the pass reads the slot's ranges and scratch)
-    } else if (pixels && !fused) {
+    } else if (args.pixels && !fused) {
         // (the slices lie back to back: one image of nviews x nrows rows in either row layout)
-        const PtToneJob tj = tone_job(j.buf, j.ncols, j.nrows * nviews, j.layout, 0, 0, pixels, format);
+        const PtToneJob tj = tone_job(j.buf, j.ncols, j.nrows * nviews, j.layout, 0, 0, args.pixels, args.format);
         e = pt_launch_tonemap(tj, st);
         if (e != hipSuccess) return fail(PT_EHIP, "tonemap launch failed: %s", hipGetErrorString(e));
     }
     return PT_OK;
 }
-
 int pt_v4_render_device_views(const pt_device_job* dj, const pt_v4_camera* cams, int32_t nviews, uint32_t* pixels,
                               int32_t format, void* stream)
 {

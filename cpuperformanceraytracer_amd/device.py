@@ -228,6 +228,49 @@ def render_v4_device_present(buf, pixels, width: int, height: int, *, frame_firs
             "pt_v4_render_device_present")
 
 
+def _v4_batch(what: str, buf, cameras, width: int, height: int, nrows, job_kw: dict, pixels, pixel_format: int, *,
+              frames=None, scenes=None, scene_of_view=None, envs=None, env_of_view=None):
+    """The arguments of a batched v4 launch, marshalled once for the four render_v4_device_* calls: (the
+    pt_device_job, a filled pt_v4_batch, the list that keeps its ctypes arrays alive).  `what` names the caller
+    in every PtError; job_kw: _job's keywords but nrows."""
+    nrows = height if nrows is None else nrows
+    cams = [(tuple(float(x) for x in pos), float(fov)) for pos, fov in cameras]
+    nviews = len(cams)
+    if any(len(pos) != 3 for pos, _ in cams):
+        raise N.PtError(N.PT_EINVAL, what, "a camera position has three components")
+    if not 1 <= nviews <= N.PT_V4_MAX_VIEWS:
+        raise N.PtError(N.PT_EINVAL, what, f"{nviews} cameras outside [1, {N.PT_V4_MAX_VIEWS}]")
+    # (_job checks the tensor against nrows: the batch as one job of V x nrows rows, then the job's own rows)
+    job = _job(buf, width, height, nrows=nviews * nrows, **job_kw)
+    job.nrows = nrows
+    if pixels is not None:
+        _check_pixels(pixels, nviews * nrows * width, buf)
+    keep = []
+
+    def per_view(m, name, ctype, conv):
+        if m is None:
+            return None
+        if len(m) != nviews:
+            raise N.PtError(N.PT_EINVAL, what, f"{name} has {len(m)} entries for {nviews} views")
+        keep.append((ctype * nviews)(*[conv(x) for x in m]))
+        return keep[-1]
+    b = N.PtV4Batch()
+    b.cams, b.nviews = per_view(cams, "cameras", N.PtV4Camera, lambda c: N.PtV4Camera((ctypes.c_float * 3)(*c[0]), c[1])), nviews
+    b.frames = per_view(frames, "frames", N.PtV4FrameRange, lambda r: N.PtV4FrameRange(int(r[0]), int(r[1])))
+    if scenes is not None:
+        descs = [v4_scene_desc(s) for s in scenes]
+        if not descs:
+            raise N.PtError(N.PT_EINVAL, what, "no scenes")
+        keep.append((N.PtV4SceneDesc * len(descs))(*descs))
+        b.scenes, b.nscenes = keep[-1], len(descs)
+    b.scene_of_view = per_view(scene_of_view, "scene_of_view", ctypes.c_int32, int)
+    b.envs = envs.handle if envs is not None else None
+    b.env_of_view = per_view(env_of_view, "env_of_view", ctypes.c_int32, int)
+    b.pixels = pixels.data_ptr() if pixels is not None else None
+    b.format = pixel_format
+    return job, b, keep
+
+
 def render_v4_device_views(buf, cameras, width: int, height: int, *, frame_first: int, nframes: int, num_bounces: int = 8,
                            row_start: int = 0, row_stride: int = 1, nrows: int | None = None,
                            layout: int = N.PT_LAYOUT_INTERLEAVED, use_env: bool = False, pixels=None,
@@ -238,21 +281,11 @@ def render_v4_device_views(buf, cameras, width: int, height: int, *, frame_first
     v4_camera(*cameras[v]) + render_v4_device on it would leave it.  pixels: an optional 32-bit tensor of
     V x nrows x width words, each slice equal to tonemap_device on its accumulator slice.  The camera of
     v4_camera and the v4 frame counter are neither read nor changed.  Asynchronous on `stream`."""
-    nrows = height if nrows is None else nrows
-    cams = [(tuple(float(x) for x in pos), float(fov)) for pos, fov in cameras]
-    nviews = len(cams)
-    if any(len(pos) != 3 for pos, _ in cams):
-        raise N.PtError(N.PT_EINVAL, "render_v4_device_views", "a camera position has three components")
-    if not 1 <= nviews <= N.PT_V4_MAX_VIEWS:
-        raise N.PtError(N.PT_EINVAL, "render_v4_device_views", f"{nviews} cameras outside [1, {N.PT_V4_MAX_VIEWS}]")
-    # (_job checks the tensor against nrows: the batch as one job of V x nrows rows, then the job's own rows)
-    job = _job(buf, width, height, row_start, row_stride, nviews * nrows, frame_first, nframes, num_bounces, layout, use_env)
-    job.nrows = nrows
-    if pixels is not None:
-        _check_pixels(pixels, nviews * nrows * width, buf)
-    arr = (N.PtV4Camera * nviews)(*[N.PtV4Camera((ctypes.c_float * 3)(*pos), fov) for pos, fov in cams])
-    N.check(N.load().pt_v4_render_device_views(ctypes.byref(job), arr, nviews, pixels.data_ptr() if pixels is not None else None,
-                                               pixel_format, _stream(stream)), "pt_v4_render_device_views")
+    job_kw = dict(row_start=row_start, row_stride=row_stride, frame_first=frame_first, nframes=nframes, num_bounces=num_bounces,
+                  layout=layout, use_env=use_env)
+    job, b, _keep = _v4_batch("render_v4_device_views", buf, cameras, width, height, nrows, job_kw, pixels, pixel_format)
+    N.check(N.load().pt_v4_render_device_views(ctypes.byref(job), b.cams, b.nviews, b.pixels, b.format, _stream(stream)),
+            "pt_v4_render_device_views")
 
 
 def v4_scene_desc(scene) -> "N.PtV4SceneDesc":
@@ -297,30 +330,15 @@ def render_v4_device_scenes(buf, scenes, cameras, width: int, height: int, scene
     description's Add*ToScene calls, v4_camera(*cameras[v]) and render_v4_device on it would leave it; the
     scene of Add*ToScene, the camera of v4_camera and the v4 frame counter are neither read nor changed.
     Asynchronous on `stream`."""
-    nrows = height if nrows is None else nrows
-    cams = [(tuple(float(x) for x in pos), float(fov)) for pos, fov in cameras]
-    nviews = len(cams)
-    if any(len(pos) != 3 for pos, _ in cams):
-        raise N.PtError(N.PT_EINVAL, "render_v4_device_scenes", "a camera position has three components")
-    if not 1 <= nviews <= N.PT_V4_MAX_VIEWS:
-        raise N.PtError(N.PT_EINVAL, "render_v4_device_scenes", f"{nviews} cameras outside [1, {N.PT_V4_MAX_VIEWS}]")
-    descs = [v4_scene_desc(s) for s in scenes]
+    descs = [v4_scene_desc(s) for s in scenes]   # (here `scenes` is not optional)
     if not descs:
         raise N.PtError(N.PT_EINVAL, "render_v4_device_scenes", "no scenes")
-    job = _job(buf, width, height, row_start, row_stride, nviews * nrows, frame_first, nframes, num_bounces, layout, use_env)
-    job.nrows = nrows
-    if pixels is not None:
-        _check_pixels(pixels, nviews * nrows * width, buf)
-    arr = (N.PtV4Camera * nviews)(*[N.PtV4Camera((ctypes.c_float * 3)(*pos), fov) for pos, fov in cams])
-    sarr = (N.PtV4SceneDesc * len(descs))(*descs)
-    smap = None
-    if scene_of_view is not None:
-        if len(scene_of_view) != nviews:
-            raise N.PtError(N.PT_EINVAL, "render_v4_device_scenes", f"scene_of_view has {len(scene_of_view)} entries for {nviews} views")
-        smap = (ctypes.c_int32 * nviews)(*[int(s) for s in scene_of_view])
-    N.check(N.load().pt_v4_render_device_scenes(ctypes.byref(job), sarr, len(descs), arr, smap, nviews,
-                                                pixels.data_ptr() if pixels is not None else None, pixel_format,
-                                                _stream(stream)), "pt_v4_render_device_scenes")
+    job_kw = dict(row_start=row_start, row_stride=row_stride, frame_first=frame_first, nframes=nframes, num_bounces=num_bounces,
+                  layout=layout, use_env=use_env)
+    job, b, _keep = _v4_batch("render_v4_device_scenes", buf, cameras, width, height, nrows, job_kw, pixels, pixel_format,
+                              scenes=descs, scene_of_view=scene_of_view)
+    N.check(N.load().pt_v4_render_device_scenes(ctypes.byref(job), b.scenes, b.nscenes, b.cams, b.scene_of_view, b.nviews,
+                                                b.pixels, b.format, _stream(stream)), "pt_v4_render_device_scenes")
 
 
 class V4EnvSet:
@@ -382,36 +400,12 @@ def render_v4_device_envs(buf, envs: V4EnvSet, cameras, width: int, height: int,
     built through ClearScene + Add*ToScene, v4_camera(*cameras[v]) and render_v4_device on it would leave it;
     the env map of set_env_map, the scene, the camera and the v4 frame counter are not changed.  Asynchronous
     on `stream`."""
-    nrows = height if nrows is None else nrows
-    cams = [(tuple(float(x) for x in pos), float(fov)) for pos, fov in cameras]
-    nviews = len(cams)
-    if any(len(pos) != 3 for pos, _ in cams):
-        raise N.PtError(N.PT_EINVAL, "render_v4_device_envs", "a camera position has three components")
-    if not 1 <= nviews <= N.PT_V4_MAX_VIEWS:
-        raise N.PtError(N.PT_EINVAL, "render_v4_device_envs", f"{nviews} cameras outside [1, {N.PT_V4_MAX_VIEWS}]")
-    job = _job(buf, width, height, row_start, row_stride, nviews * nrows, frame_first, nframes, num_bounces, layout, use_env)
-    job.nrows = nrows
-    if pixels is not None:
-        _check_pixels(pixels, nviews * nrows * width, buf)
-    arr = (N.PtV4Camera * nviews)(*[N.PtV4Camera((ctypes.c_float * 3)(*pos), fov) for pos, fov in cams])
-
-    def mapping(m, what):
-        if m is None:
-            return None
-        if len(m) != nviews:
-            raise N.PtError(N.PT_EINVAL, "render_v4_device_envs", f"{what} has {len(m)} entries for {nviews} views")
-        return (ctypes.c_int32 * nviews)(*[int(x) for x in m])
-    sarr, nscenes = None, 0
-    if scenes is not None:
-        descs = [v4_scene_desc(s) for s in scenes]
-        if not descs:
-            raise N.PtError(N.PT_EINVAL, "render_v4_device_envs", "no scenes")
-        sarr, nscenes = (N.PtV4SceneDesc * len(descs))(*descs), len(descs)
-    N.check(N.load().pt_v4_render_device_envs(ctypes.byref(job), envs.handle if envs is not None else None,
-                                              mapping(env_of_view, "env_of_view"), sarr, nscenes,
-                                              mapping(scene_of_view, "scene_of_view"), arr, nviews,
-                                              pixels.data_ptr() if pixels is not None else None, pixel_format,
-                                              _stream(stream)), "pt_v4_render_device_envs")
+    job_kw = dict(row_start=row_start, row_stride=row_stride, frame_first=frame_first, nframes=nframes, num_bounces=num_bounces,
+                  layout=layout, use_env=use_env)
+    job, b, _keep = _v4_batch("render_v4_device_envs", buf, cameras, width, height, nrows, job_kw, pixels, pixel_format,
+                              scenes=scenes, scene_of_view=scene_of_view, envs=envs, env_of_view=env_of_view)
+    N.check(N.load().pt_v4_render_device_envs(ctypes.byref(job), b.envs, b.env_of_view, b.scenes, b.nscenes, b.scene_of_view,
+                                              b.cams, b.nviews, b.pixels, b.format, _stream(stream)), "pt_v4_render_device_envs")
 
 
 def render_v4_device_batch(buf, cameras, width: int, height: int, *, frames=None, scenes=None, scene_of_view=None, envs=None,
@@ -432,57 +426,18 @@ def render_v4_device_batch(buf, cameras, width: int, height: int, *, frames=None
     view's 8-bit image (the v4_config's tonemap pair; R, G, B) moved in this launch: columns 0 and 1 are the low
     and high word of sum_delta, column 2 is `changed`, column 3 is max_delta (v4_view_stats reads them).  A view
     of 0 frames has zeros.  Read it after the stream reaches the call."""
-    nrows = height if nrows is None else nrows
-    cams = [(tuple(float(x) for x in pos), float(fov)) for pos, fov in cameras]
-    nviews = len(cams)
-    if any(len(pos) != 3 for pos, _ in cams):
-        raise N.PtError(N.PT_EINVAL, "render_v4_device_batch", "a camera position has three components")
-    if not 1 <= nviews <= N.PT_V4_MAX_VIEWS:
-        raise N.PtError(N.PT_EINVAL, "render_v4_device_batch", f"{nviews} cameras outside [1, {N.PT_V4_MAX_VIEWS}]")
-    if use_env is None:
-        use_env = envs is not None
-    job = _job(buf, width, height, row_start, row_stride, nviews * nrows, frame_first, nframes, num_bounces, layout, use_env)
-    job.nrows = nrows
-    if pixels is not None:
-        _check_pixels(pixels, nviews * nrows * width, buf)
-    keep = [(N.PtV4Camera * nviews)(*[N.PtV4Camera((ctypes.c_float * 3)(*pos), fov) for pos, fov in cams])]
-
-    def per_view(m, what, ctype, conv):
-        if m is None:
-            return None
-        if len(m) != nviews:
-            raise N.PtError(N.PT_EINVAL, "render_v4_device_batch", f"{what} has {len(m)} entries for {nviews} views")
-        keep.append((ctype * nviews)(*[conv(x) for x in m]))
-        return keep[-1]
-    b = N.PtV4Batch()
-    b.cams, b.nviews = keep[0], nviews
-    farr = per_view(frames, "frames", N.PtV4FrameRange, lambda r: N.PtV4FrameRange(int(r[0]), int(r[1])))
-    if farr is not None:
-        b.frames = farr
-    if scenes is not None:
-        descs = [v4_scene_desc(s) for s in scenes]
-        if not descs:
-            raise N.PtError(N.PT_EINVAL, "render_v4_device_batch", "no scenes")
-        keep.append((N.PtV4SceneDesc * len(descs))(*descs))
-        b.scenes, b.nscenes = keep[-1], len(descs)
-    smap = per_view(scene_of_view, "scene_of_view", ctypes.c_int32, int)
-    if smap is not None:
-        b.scene_of_view = smap
-    if envs is not None:
-        b.envs = envs.handle
-    emap = per_view(env_of_view, "env_of_view", ctypes.c_int32, int)
-    if emap is not None:
-        b.env_of_view = emap
-    b.pixels = pixels.data_ptr() if pixels is not None else None
-    b.format = pixel_format
+    job_kw = dict(row_start=row_start, row_stride=row_stride, frame_first=frame_first, nframes=nframes, num_bounces=num_bounces,
+                  layout=layout, use_env=envs is not None if use_env is None else use_env)
+    job, b, _keep = _v4_batch("render_v4_device_batch", buf, cameras, width, height, nrows, job_kw, pixels, pixel_format,
+                              frames=frames, scenes=scenes, scene_of_view=scene_of_view, envs=envs, env_of_view=env_of_view)
     if stats is None:
         N.check(N.load().pt_v4_render_device_batch(ctypes.byref(job), ctypes.byref(b), _stream(stream)), "pt_v4_render_device_batch")
         return
     import torch
     if (not isinstance(stats, torch.Tensor) or stats.device != buf.device or stats.dtype != torch.int32 or
-            tuple(stats.shape) != (nviews, 4) or not stats.is_contiguous()):
+            tuple(stats.shape) != (b.nviews, 4) or not stats.is_contiguous()):
         raise N.PtError(N.PT_EINVAL, "render_v4_device_batch",
-                        f"stats must be a contiguous int32 tensor of {nviews} x 4 on the buffer's device")
+                        f"stats must be a contiguous int32 tensor of {b.nviews} x 4 on the buffer's device")
     N.check(N.load().pt_v4_render_device_batch_stats(ctypes.byref(job), ctypes.byref(b), stats.data_ptr(), _stream(stream)),
             "pt_v4_render_device_batch_stats")
 
